@@ -1,6 +1,13 @@
 """Benchmark: Gvoxels/s of thresholded CCL end to end on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode greater|less] [--mask]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what
+takes runs of its own: the per-kernel breakdown (`kernels_ms_per_step`, `host_per_step`: the same
+steps again with an event pair around every launch), `cpu_baseline` (the oracle on host cores) and,
+for --workload c1, `cold_start`.  --dump-outputs DIR writes what the last timed step returned
+(dump_outputs below).
 
 One step = the full five-stage path (block_components -> merge_offsets -> block_faces ->
 merge_assignments -> write) over one synthetic volume that is already resident in HBM,
@@ -86,13 +93,22 @@ def parse(argv=None):
                         'c5 ((256N,4096,4096), weak), c2 (512^3, block 128^3), c1 (125x1250x1250, block '
                         '50x512x512, + cold_start)')
     p.add_argument('--block-shape', default=None)
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='also measure what takes runs of its own: the per-kernel breakdown, the CPU baseline, '
+                        "and workload c1's cold start")
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='after the timed steps, write what the last timed step returned as DIR/<name>.npy '
+                        '(a fixed, seeded sample of the labels; see dump_outputs)')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     p.add_argument('--cpu-sample-z', type=int, default=1024)
     p.add_argument('--cold-child', default=None, help=argparse.SUPPRESS)   # internal: see cold_start()
     p.add_argument('--traffic-json', default=None,
                    help='tools/prof_summary.py output (rocprofv3 FETCH_SIZE / WRITE_SIZE passes) to fill '
                         'roofline.traffic; default profiles/traffic_<workload tag>.json when present')
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def launcher_cmd(gpus, argv, port, script=None):
@@ -215,6 +231,31 @@ def load_traffic(path, kernel, lib_src):
     return None, src
 
 
+DUMP_SEED = 0x5EED
+DUMP_SAMPLES = 1 << 21         # voxels sampled over all ranks: 2 x 16 MiB of float64 (ids, indices)
+
+
+def dump_outputs(path, labels, res, rank=0, world=1):
+    """Write what the timed path returned in its last step: the uint64 labels (as float64, exact
+    below 2^53) at a fixed, seeded sample of this rank's voxels, the sample's flat indices into the
+    rank's slab, and the counts of the result.  Inputs and sample are the same from run to run, so
+    the files of two builds compare value for value.  One file set per rank at N > 1."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    flat = labels.reshape(-1)
+    n = min(flat.numel(), DUMP_SAMPLES // world)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=n, dtype=np.int64)
+                  if n < flat.numel() else np.arange(n, dtype=np.int64))
+    ids = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().view(np.uint64)
+    assert ids.size == 0 or int(ids.max()) < 2 ** 53, 'label ids beyond float64 integers'
+    sfx = '' if world == 1 else '_rank%d' % rank
+    np.save(os.path.join(path, 'labels_sample%s.npy' % sfx), ids.astype(np.float64))
+    np.save(os.path.join(path, 'labels_sample_index%s.npy' % sfx), idx.astype(np.float64))
+    np.save(os.path.join(path, 'counts%s.npy' % sfx),
+            np.array([res[k] for k in ('n_labels', 'max_id', 'n_components') if k in res], dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.cold_child:
@@ -314,13 +355,17 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     prof = ctx.profile()
-    # per-kernel breakdown: the same steps again (untimed), an event pair around every launch
-    ctx.set_profiling(1)
-    ctx.reset_profile()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    breakdown = ctx.profile()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, res, rank, world)
+    breakdown = {}
+    if args.full:
+        # per-kernel breakdown: the same steps again (untimed), an event pair around every launch
+        ctx.set_profiling(1)
+        ctx.reset_profile()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        breakdown = ctx.profile()
     ctx.set_profiling(False)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if backend == 'nccl' else 'cpu')
@@ -377,20 +422,21 @@ def main():
         'roofline': roofline,
         'e2e_roofline': {'alg_bytes_per_voxel': b_alg, 'achieved_gbs_per_gpu': round(e2e_gbs, 1),
                          'frac': round(e2e_gbs / HBM_PEAK_GBS, 4)},
-        'kernels_ms_per_step': {k: round(v['total_ms'] / args.steps, 4) for k, v in
-                                sorted(breakdown.items(), key=lambda kv: -kv[1]['total_ms']) if v['count']},
-        'host_per_step': {k: {'count': v['count'] / args.steps, 'ms': round(v['total_ms'] / args.steps, 4)}
-                          for k, v in host.items()},
         'result': res,
         'lib': {'version': _lib.version(), 'src': lib_src},
     }
-    if wl == 'c1' and world == 1:
+    if args.full:
+        line['kernels_ms_per_step'] = {k: round(v['total_ms'] / args.steps, 4) for k, v in
+                                       sorted(breakdown.items(), key=lambda kv: -kv[1]['total_ms']) if v['count']}
+        line['host_per_step'] = {k: {'count': v['count'] / args.steps, 'ms': round(v['total_ms'] / args.steps, 4)}
+                                 for k, v in host.items()}
+    if args.full and wl == 'c1' and world == 1:
         line['cold_start'] = cold_start(args, x, block_shape)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         del x, out
         torch.cuda.empty_cache()
         line['cpu_baseline'] = cpu_baseline(args, block_shape, slab[1:], slab[0])
-    elif rank == 0:
+    elif args.full and rank == 0:
         line['cpu_baseline'] = None
     if rank == 0:
         print(json.dumps(line), flush=True)

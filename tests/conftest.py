@@ -43,8 +43,21 @@ def golden_index():
 def load_golden(name):
     d = np.load(os.path.join(GOLDEN, name + '.npz'))
     out = {k: d[k] for k in d.files}
-    if 'input' not in out:
+    if 'input' not in out and 'input_q' in out:
         out['input'] = out['input_q'].astype(np.float32) / np.float32(256)
+    elif 'input' not in out:
+        # a large multi-channel input stored channel by channel in files of its own, shared by the
+        # cases that use it (make_golden_channel.pack_input): `input_c<i>_q` uint8 where the
+        # channel is exactly q / 256, `input_c<i>` as it is otherwise
+        for side in out.pop('input_files'):
+            s = np.load(os.path.join(GOLDEN, str(side) + '.npz'))
+            out.update({k: s[k] for k in s.files})
+        chans = []
+        while 'input_c%d' % len(chans) in out or 'input_c%d_q' % len(chans) in out:
+            i = len(chans)
+            chans.append(out.pop('input_c%d' % i) if 'input_c%d' % i in out
+                         else out.pop('input_c%d_q' % i).astype(np.float32) / np.float32(256))
+        out['input'] = np.stack(chans)
     return out
 
 

@@ -15,8 +15,10 @@ float64 for them), an int channel, repeated and reordered channel lists, a mask.
 
 Output: tests/golden/channel_<case>.npz (input, channel list, the reference artefacts as in
 make_golden.py, and `thr_expected` = the reference threshold job's uint8 output) and
-tests/golden/index_channel.json.
+tests/golden/index_channel.json; a large input goes to tests/golden/chaninput_<hash>_*.npz
+(pack_input), shared by the cases that use it.
 """
+import hashlib
 import json
 import os
 import shutil
@@ -95,6 +97,28 @@ def make_cases():
     return cases
 
 
+PACK_BYTES = 1 << 20       # inputs of this size and more are stored channel by channel
+
+
+def pack_input(inp):
+    """How an input is stored -> (arrays of the case's file, {side file: arrays}).  `input` as it is,
+    or, for a large float32 input, channel by channel in side files named after the input's hash
+    (cases with the same input share them; conftest.load_golden stacks the channels again, bit for
+    bit): `input_c<i>_q` uint8 where the channel is exactly q / 256, all of them in one file, and
+    `input_c<i>` otherwise, a file each.  Keeps every file below 1 MiB."""
+    if inp.dtype != np.float32 or inp.nbytes < PACK_BYTES:
+        return {'input': inp}, {}
+    stem = 'chaninput_' + hashlib.sha256(inp.tobytes()).hexdigest()[:12]
+    sides = {}
+    for i, c in enumerate(inp):
+        q = c * np.float32(256)
+        if np.array_equal(q, np.round(q)) and q.min() >= 0 and q.max() <= 255:
+            sides.setdefault(stem + '_q', {})['input_c%d_q' % i] = q.astype(np.uint8)
+        else:
+            sides[stem + '_c%d' % i] = {'input_c%d' % i: c}
+    return {'input_files': np.array(sorted(sides))}, sides
+
+
 def main():
     index = {}
     for c in make_cases():
@@ -103,7 +127,7 @@ def main():
         thr = run_reference_threshold(c['inp'], c['block_shape'], c['threshold'], c['mode'], c['channel'])
         chans = [c['channel']] if isinstance(c['channel'], int) else list(c['channel'])
         arrays = dict(
-            input=c['inp'], channel=np.array(chans, dtype=np.int64),
+            channel=np.array(chans, dtype=np.int64),
             block_shape=np.array(c['block_shape'], dtype=np.int64),
             threshold=np.array(c['threshold'], dtype=np.float64),
             block_values=res['block_values'], offsets=res['offsets'],
@@ -111,6 +135,10 @@ def main():
             local_labels=res['local_labels'].astype(np.uint32), pairs=res['pairs'],
             lut_canon=canon(res['lut']), labels_canon=canon(res['labels']),
             max_id=np.array(res['max_id'], dtype=np.uint64), thr_expected=thr.astype(np.uint8))
+        packed, sides = pack_input(c['inp'])
+        arrays.update(packed)
+        for side, side_arrays in sides.items():
+            np.savez_compressed(os.path.join(HERE, side + '.npz'), **side_arrays)
         if c['mask'] is not None:
             arrays['mask'] = c['mask']
         np.savez_compressed(os.path.join(HERE, 'channel_%s.npz' % c['name']), **arrays)

@@ -91,3 +91,35 @@ def test_traffic_file_provenance(tmp_path):
     assert bench.load_traffic(str(p), 'k_pass2', 'abc') == (34940478334, 'abc')
     assert bench.load_traffic(str(p), 'k_spec', 'abc') == (18212456067, 'abc')
     assert bench.load_traffic(str(tmp_path / 'none.json'), 'k_pass2', 'abc') == (None, None)
+
+
+def test_full_and_dump_options():
+    """A plain run is the headline line only: --full and --dump-outputs are off by default."""
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(['--full', '--dump-outputs', 'd', '--steps', '4'])
+    assert a.full is True and a.dump_outputs == 'd' and a.steps == 4
+    with pytest.raises(SystemExit):
+        bench.parse(['--steps', '0'])
+
+
+def test_dump_outputs_is_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files of a seeded sample; the same sample on every call, the
+    whole volume when it is smaller than the sample."""
+    import numpy as np
+    import torch
+    lab = torch.arange(5 * 6 * 7, dtype=torch.int64).reshape(5, 6, 7) * 3
+    res = {'n_labels': 11, 'max_id': 10, 'n_components': 12, 'n_blocks': 4}
+    bench.dump_outputs(str(tmp_path / 'a'), lab, res)
+    got = {f: np.load(str(tmp_path / 'a' / f)) for f in sorted(os.listdir(str(tmp_path / 'a')))}
+    assert sorted(got) == ['counts.npy', 'labels_sample.npy', 'labels_sample_index.npy']
+    assert all(v.dtype == np.float64 for v in got.values())
+    np.testing.assert_array_equal(got['labels_sample.npy'], np.arange(210) * 3.0)
+    np.testing.assert_array_equal(got['counts.npy'], [11, 10, 12])
+    monkeypatch.setattr(bench, 'DUMP_SAMPLES', 64)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), lab, res, rank=1, world=2)
+    idx = np.load(str(tmp_path / 'b' / 'labels_sample_index_rank1.npy'))
+    assert idx.shape == (32,) and np.all(np.diff(idx) >= 0) and idx.max() < 210
+    np.testing.assert_array_equal(idx, np.load(str(tmp_path / 'c' / 'labels_sample_index_rank1.npy')))
+    np.testing.assert_array_equal(np.load(str(tmp_path / 'b' / 'labels_sample_rank1.npy')), idx * 3.0)

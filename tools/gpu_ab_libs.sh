@@ -8,6 +8,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do V+=("$1"); shift; done
 [ "$1" = "--" ] && shift
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"; mkdir -p gpurun_out
+O=${OUT_DIR:-bench_out}; mkdir -p "$O"      # where the bench lines go
 for n in "${V[@]}"; do
   CC_LIB_PATH=$ROOT/tools/ab/lib_$n.so timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -m gpu -q -x \
       --timeout 120 --timeout-method thread -k "${AB_TESTS:-synthetic_vs_oracle or white_noise or max_runs or speculated}" \
@@ -16,10 +17,10 @@ for n in "${V[@]}"; do
 done
 for i in $(seq 1 ${ROUNDS:-3}); do
   for n in "${V[@]}"; do
-    CC_LIB_PATH=$ROOT/tools/ab/lib_$n.so timeout -k 10 150 python -u bench.py --no-cpu-baseline --steps 10 "$@" \
-        > gpurun_out/ab_$n.json 2> gpurun_out/ab_$n.err
+    CC_LIB_PATH=$ROOT/tools/ab/lib_$n.so timeout -k 10 150 python -u bench.py --full --no-cpu-baseline --steps 10 "$@" \
+        > $O/ab_$n.json 2> $O/ab_$n.err
     python3 -c "
-import json; d=json.loads(open('gpurun_out/ab_$n.json').read().strip().splitlines()[-1])
+import json; d=json.loads(open('$O/ab_$n.json').read().strip().splitlines()[-1])
 print('$n', d['ms_per_step'], {k: v for k, v in list(d['kernels_ms_per_step'].items())[:4]})"
   done
 done

@@ -15,10 +15,10 @@ tools/profile.sh ${TAG}_c3_cont --steps 10 --warmup 3 --dither
 tools/profile.sh ${TAG}_c2 --workload c2 --steps 20 --warmup 5
 tools/profile.sh ${TAG}_c1 --workload c1 --steps 20 --warmup 5
 tools/profile.sh ${TAG}_c5 --workload c5 --steps 10 --warmup 3
-timeout -k 10 300 python -u bench.py --traffic-json $O/prof_${TAG}_c3/summary.json > $O/final_bench_$TAG.json 2> $O/final_bench_$TAG.err
+timeout -k 10 300 python -u bench.py --full --traffic-json $O/prof_${TAG}_c3/summary.json > $O/final_bench_$TAG.json 2> $O/final_bench_$TAG.err
 cat $O/final_bench_$TAG.json
 for w in c4 c2 c1 c5; do
-  timeout -k 10 240 python -u bench.py --no-cpu-baseline --workload $w --traffic-json $O/prof_${TAG}_$w/summary.json \
+  timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --workload $w --traffic-json $O/prof_${TAG}_$w/summary.json \
       > $O/final_bench_${w}_$TAG.json 2> $O/final_bench_${w}_$TAG.err
   tail -c 400 $O/final_bench_${w}_$TAG.json; echo
 done

@@ -37,25 +37,25 @@ PYT="python -u -m pytest -x -v --timeout 400 --timeout-method thread"
 for step in "$@"; do
   echo "== $step $(date +%T)"
   case $step in
-    bench)      timeout -k 10 240 python -u bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_$TAG.json 2> $O/bench_$TAG.err; cat $O/bench_$TAG.json ;;
-    bench_full) timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > $O/bench_full_$TAG.json 2> $O/bench_full_$TAG.err; cat $O/bench_full_$TAG.json ;;
-    bench_c4)   timeout -k 10 240 python -u bench.py --no-cpu-baseline --workload c4 --steps 20 --warmup 5 > $O/bench_c4_$TAG.json 2> $O/bench_c4_$TAG.err; cat $O/bench_c4_$TAG.json ;;
-    bench_c4_sync) CC_FAST=0 timeout -k 10 240 python -u bench.py --no-cpu-baseline --workload c4 --steps 20 --warmup 5 > $O/bench_c4_sync_$TAG.json 2> $O/bench_c4_sync_$TAG.err; cat $O/bench_c4_sync_$TAG.json ;;
-    bench_c1_sync) CC_FAST=0 timeout -k 10 240 python -u bench.py --no-cpu-baseline --workload c1 --steps 50 --warmup 10 > $O/bench_c1_sync_$TAG.json 2> $O/bench_c1_sync_$TAG.err; cat $O/bench_c1_sync_$TAG.json ;;
-    bench_c2)   timeout -k 10 240 python -u bench.py --no-cpu-baseline --workload c2 --steps 50 --warmup 10 > $O/bench_c2_$TAG.json 2> $O/bench_c2_$TAG.err; cat $O/bench_c2_$TAG.json ;;
-    bench_c1)   timeout -k 10 240 python -u bench.py --no-cpu-baseline --workload c1 --steps 50 --warmup 10 > $O/bench_c1_$TAG.json 2> $O/bench_c1_$TAG.err; cat $O/bench_c1_$TAG.json ;;
-    bench_cont) timeout -k 10 240 python -u bench.py --no-cpu-baseline --dither --steps 20 --warmup 5 > $O/bench_cont_$TAG.json 2> $O/bench_cont_$TAG.err; cat $O/bench_cont_$TAG.json ;;
-    bench_c2_sync) CC_FAST=0 timeout -k 10 240 python -u bench.py --no-cpu-baseline --workload c2 --steps 50 --warmup 10 > $O/bench_c2_sync_$TAG.json 2> $O/bench_c2_sync_$TAG.err; cat $O/bench_c2_sync_$TAG.json ;;
-    bench_sync) CC_FAST=0 timeout -k 10 240 python -u bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_sync_$TAG.json 2> $O/bench_sync_$TAG.err; cat $O/bench_sync_$TAG.json ;;
+    bench)      timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_$TAG.json 2> $O/bench_$TAG.err; cat $O/bench_$TAG.json ;;
+    bench_full) timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > $O/bench_full_$TAG.json 2> $O/bench_full_$TAG.err; cat $O/bench_full_$TAG.json ;;
+    bench_c4)   timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --workload c4 --steps 20 --warmup 5 > $O/bench_c4_$TAG.json 2> $O/bench_c4_$TAG.err; cat $O/bench_c4_$TAG.json ;;
+    bench_c4_sync) CC_FAST=0 timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --workload c4 --steps 20 --warmup 5 > $O/bench_c4_sync_$TAG.json 2> $O/bench_c4_sync_$TAG.err; cat $O/bench_c4_sync_$TAG.json ;;
+    bench_c1_sync) CC_FAST=0 timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --workload c1 --steps 50 --warmup 10 > $O/bench_c1_sync_$TAG.json 2> $O/bench_c1_sync_$TAG.err; cat $O/bench_c1_sync_$TAG.json ;;
+    bench_c2)   timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --workload c2 --steps 50 --warmup 10 > $O/bench_c2_$TAG.json 2> $O/bench_c2_$TAG.err; cat $O/bench_c2_$TAG.json ;;
+    bench_c1)   timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --workload c1 --steps 50 --warmup 10 > $O/bench_c1_$TAG.json 2> $O/bench_c1_$TAG.err; cat $O/bench_c1_$TAG.json ;;
+    bench_cont) timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --dither --steps 20 --warmup 5 > $O/bench_cont_$TAG.json 2> $O/bench_cont_$TAG.err; cat $O/bench_cont_$TAG.json ;;
+    bench_c2_sync) CC_FAST=0 timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --workload c2 --steps 50 --warmup 10 > $O/bench_c2_sync_$TAG.json 2> $O/bench_c2_sync_$TAG.err; cat $O/bench_c2_sync_$TAG.json ;;
+    bench_sync) CC_FAST=0 timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_sync_$TAG.json 2> $O/bench_sync_$TAG.err; cat $O/bench_sync_$TAG.json ;;
     tests_parity) timeout -k 10 900 $PYT tests/test_gpu_parity.py tests/test_watershed.py tests/test_gpu_workflow.py > $O/tests_parity_$TAG.log 2>&1 || { tail -40 $O/tests_parity_$TAG.log; exit 1; }; tail -3 $O/tests_parity_$TAG.log ;;
     slabs8_c3)  timeout -k 10 300 python -u tools/bench_sharded_slabs.py 8 c3 10 > $O/slabs8_c3_$TAG.json 2> $O/slabs8_c3_$TAG.err; cat $O/slabs8_c3_$TAG.json ;;
     slabs8_c4)  timeout -k 10 300 python -u tools/bench_sharded_slabs.py 8 c4 10 > $O/slabs8_c4_$TAG.json 2> $O/slabs8_c4_$TAG.err; cat $O/slabs8_c4_$TAG.json ;;
-    n4gloo)     CC_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --gpus 4 --workload c3 --steps 5 --warmup 2 --no-cpu-baseline > $O/n4gloo_$TAG.json 2> $O/n4gloo_$TAG.err; cat $O/n4gloo_$TAG.json ;;
-    n2gloo)     CC_DIST_BACKEND=gloo timeout -k 10 300 python -u bench.py --gpus 2 --workload c4 --steps 5 --warmup 2 --no-cpu-baseline > $O/n2gloo_$TAG.json 2> $O/n2gloo_$TAG.err; cat $O/n2gloo_$TAG.json ;;
+    n4gloo)     CC_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --full --gpus 4 --workload c3 --steps 5 --warmup 2 --no-cpu-baseline > $O/n4gloo_$TAG.json 2> $O/n4gloo_$TAG.err; cat $O/n4gloo_$TAG.json ;;
+    n2gloo)     CC_DIST_BACKEND=gloo timeout -k 10 300 python -u bench.py --full --gpus 2 --workload c4 --steps 5 --warmup 2 --no-cpu-baseline > $O/n2gloo_$TAG.json 2> $O/n2gloo_$TAG.err; cat $O/n2gloo_$TAG.json ;;
     tests)      timeout -k 10 1000 $PYT tests -m gpu > $O/tests_$TAG.log 2>&1 || { tail -40 $O/tests_$TAG.log; exit 1; }; tail -3 $O/tests_$TAG.log ;;
     smoke)      timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_$TAG.log 2>&1 || { tail -20 $O/smoke_$TAG.log; exit 1; }; tail -3 $O/smoke_$TAG.log ;;
     tests_comm) timeout -k 10 600 $PYT tests/test_gpu_comm.py tests/test_gpu_comm_ranks.py > $O/tests_comm_$TAG.log 2>&1 || { tail -40 $O/tests_comm_$TAG.log; exit 1; }; tail -3 $O/tests_comm_$TAG.log ;;
-    bench_c5)   timeout -k 10 300 python -u bench.py --no-cpu-baseline --workload c5 --steps 20 --warmup 5 > $O/bench_c5_$TAG.json 2> $O/bench_c5_$TAG.err; cat $O/bench_c5_$TAG.json ;;
+    bench_c5)   timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --workload c5 --steps 20 --warmup 5 > $O/bench_c5_$TAG.json 2> $O/bench_c5_$TAG.err; cat $O/bench_c5_$TAG.json ;;
     c1_dropin)  timeout -k 10 600 python -u tools/bench_c1.py --repeats 3 > $O/c1_dropin_$TAG.json 2> $O/c1_dropin_$TAG.err; cat $O/c1_dropin_$TAG.json ;;
     tests_workflow) timeout -k 10 900 $PYT tests/test_gpu_workflow.py > $O/tests_workflow_$TAG.log 2>&1 || { tail -40 $O/tests_workflow_$TAG.log; exit 1; }; tail -3 $O/tests_workflow_$TAG.log ;;
     tests_sharded) timeout -k 10 900 $PYT tests/test_gpu_sharded.py > $O/tests_sharded_$TAG.log 2>&1 || { tail -40 $O/tests_sharded_$TAG.log; exit 1; }; tail -3 $O/tests_sharded_$TAG.log ;;
@@ -86,7 +86,7 @@ for step in "$@"; do
                   timeout -k 5 60 amd-smi static -g 0 2>&1 || true; timeout -k 5 60 amd-smi metric -g 0 2>&1 || true; } > $O/boxinfo_$TAG.txt
                 grep -iE "vbios|power cap|max.*power|sclk|mclk|fclk|partition|Card Series|Market" $O/boxinfo_$TAG.txt | head -40 || true ;;
     clockprobe) timeout -k 10 120 tools/clock_probe 1024 2048 2048 64 512 512 4 > $O/clockprobe_$TAG.txt 2>&1; cat $O/clockprobe_$TAG.txt ;;
-    slowdiag)   timeout -k 10 240 python -u bench.py --no-cpu-baseline --steps 10 --warmup 3 > $O/sd_bench_$TAG.json 2> $O/sd_bench_$TAG.err
+    slowdiag)   timeout -k 10 240 python -u bench.py --full --no-cpu-baseline --steps 10 --warmup 3 > $O/sd_bench_$TAG.json 2> $O/sd_bench_$TAG.err
                 KS=$(python3 -c "import json; d = json.loads(open('$O/sd_bench_$TAG.json').read().strip().splitlines()[-1]); print(d['kernels_ms_per_step']['k_spec'])")
                 echo "k_spec $KS ms"
                 if python3 -c "import sys; sys.exit(0 if $KS > 3.3 else 1)"; then

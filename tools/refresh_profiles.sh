@@ -10,5 +10,6 @@ cd "$ROOT"
 mkdir -p gpurun_out
 tools/profile.sh "${TAG}_c3" --steps 10 --warmup 3
 tools/profile.sh "${TAG}_c3_mask" --steps 10 --warmup 3 --mask
-timeout -k 10 300 python3 bench.py > gpurun_out/bench_default_$TAG.json 2> gpurun_out/bench_default_$TAG.err
-cat gpurun_out/bench_default_$TAG.json
+O=${OUT_DIR:-bench_out}; mkdir -p "$O"      # where the bench lines go
+timeout -k 10 300 python3 bench.py --full > $O/bench_default_$TAG.json 2> $O/bench_default_$TAG.err
+cat $O/bench_default_$TAG.json

@@ -1,4 +1,4 @@
-"""dev: compare per-kernel times of two bench lines (JSON files given as arguments)."""
+"""dev: compare per-kernel times of two `bench.py --full` lines (JSON files given as arguments)."""
 import json
 import sys
 
