@@ -30,6 +30,7 @@ EXPORTS = (
     'cc_watershed_from_seeds', 'cc_shard_dev_begin', 'cc_shard_dev_assign', 'cc_shard_dev_top_cubes',
     'cc_shard_dev_seam_pairs', 'cc_shard_dev_finish', 'cc_normalize_channels', 'cc_shard_dev_ok',
     'cc_comm_unique_id', 'cc_comm_create', 'cc_comm_destroy', 'cc_label_volume_sharded', 'cc_comm_info',
+    'cc_label_sizes', 'cc_size_filter',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -64,6 +65,18 @@ class CCEvalResult(ctypes.Structure):
     def as_dict(self):
         return {k: (float if t is ctypes.c_double else int)(getattr(self, k)) for k, t in self._fields_}
 
+
+class CCSizeFilterResult(ctypes.Structure):
+    _fields_ = [('n_unique', ctypes.c_uint64), ('n_discarded', ctypes.c_uint64), ('n_kept', ctypes.c_uint64),
+                ('start_label', ctypes.c_uint64), ('max_id', ctypes.c_uint64),
+                ('n_voxels_discarded', ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# selections of cc_size_filter (CC_SF_* of include/cc_mi355x.h)
+SF_SIZE_THRESHOLD, SF_TARGET_NUMBER, SF_DISCARD_IDS = 0, 1, 2
 
 _lib = None
 _host_only = False
@@ -142,6 +155,8 @@ def load(host_only=False):
         'cc_evaluate': (I, [P, P, P, P, P, I, u64, ctypes.POINTER(CCEvalResult)]),
         'cc_get_overlaps': (i64, [P, P, P, P, i64]),
         'cc_relabel_consecutive': (I, [P, P, P, i64, P, P, P, i64]),
+        'cc_label_sizes': (I, [P, P, i64, P, P, P, i64]),
+        'cc_size_filter': (I, [P, P, P, i64, I, u64, P, i64, I, ctypes.POINTER(CCSizeFilterResult), P, P, P, i64]),
         'cc_channel_mean': (I, [P, P, I, P, P, i64, P]),
         'cc_gaussian_smooth_blocks': (I, [P, P, P, P, ctypes.c_double, P]),
         'cc_gaussian_taps': (I, [ctypes.c_double, P, I]),
@@ -601,6 +616,87 @@ class Context:
         uniq = uniq[:n]
         table = np.stack([uniq, np.arange(int(st[0]), int(st[0]) + n, dtype=np.uint64)], axis=1)
         return out, table
+
+    @staticmethod
+    def _check_labels(labels):
+        import torch
+        assert hasattr(labels, 'data_ptr') and labels.is_cuda and labels.element_size() == 8
+        assert labels.is_contiguous() and labels.dtype in (torch.int64, torch.uint64)
+        torch.cuda.current_stream(labels.device).synchronize()
+
+    def label_sizes(self, labels, cap_hint=1 << 20):
+        """FindUniques(return_counts=True) (relabel/find_uniques.py:105-179) over the whole volume
+        on device: returns (ids, counts), the sorted distinct ids of the uint64 (torch int64 /
+        uint64) CUDA tensor `labels` and their voxel counts, as np.unique(return_counts=True)
+        gives them.  cap_hint: the expected number of distinct ids (a larger count costs a second
+        call)."""
+        self._check_labels(labels)
+        L = load()
+        nu = np.zeros(1, dtype=np.uint64)
+        cap = max(1, int(cap_hint))
+        while True:
+            ids, counts = np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
+            _check(L.cc_label_sizes(self._h, _ptr(labels), labels.numel(), _ptr(nu), _ptr(ids), _ptr(counts), cap))
+            if int(nu[0]) <= cap:
+                break
+            cap = int(nu[0])
+        n = int(nu[0])
+        return ids[:n].copy(), counts[:n].copy()
+
+    def size_filter(self, labels, size_threshold=None, target_number=None, discard_ids=None, relabel=True,
+                    out=None, cap_hint=1 << 20):
+        """SizeFilterWorkflow (postprocess/postprocess_workflow.py:24-110) on device, in two passes
+        over the volume.  Exactly one selection: size_threshold (ids with fewer voxels are
+        discarded, size_filter_blocks.py:112), target_number (the ids with the largest counts are
+        kept; among equal counts the larger id first) or discard_ids (an explicit list; absent ids
+        are ignored).  Discarded ids become 0; relabel: the result is also relabelled
+        consecutively (find_labeling.py:106-116 over the filtered volume).  out may be `labels`
+        (in place).  Returns (out, info): info['ids'] / ['counts'] the input's sorted ids and
+        voxel counts, ['discard_ids'] the occurring ids that were discarded (sorted),
+        ['assignments'] the (m, 2) uint64 [old id, new id] table over the filtered volume's ids
+        (both columns equal without relabel), ['max_id'] the output's largest id, and the
+        counters of cc_size_filter_result."""
+        import torch
+        n_sel = sum(x is not None for x in (size_threshold, target_number, discard_ids))
+        assert n_sel == 1, 'exactly one of size_threshold, target_number, discard_ids'
+        self._check_labels(labels)
+        if out is None:
+            out = torch.empty_like(labels)
+        assert out.shape == labels.shape and out.is_contiguous() and out.element_size() == 8
+        dis, value = None, 0
+        if size_threshold is not None:
+            sel, value = SF_SIZE_THRESHOLD, int(size_threshold)
+        elif target_number is not None:
+            sel, value = SF_TARGET_NUMBER, int(target_number)
+        else:
+            sel = SF_DISCARD_IDS
+            dis = np.ascontiguousarray(np.asarray(discard_ids, dtype=np.uint64).ravel())
+        assert 0 <= value < 1 << 64
+        L = load()
+        res = CCSizeFilterResult()
+        cap = max(1, int(cap_hint))
+        while True:
+            # a table larger than cap is reported (n_unique) before out is touched, so in-place
+            # calls are safe: the second call has the exact size
+            ids, counts, new = (np.empty(cap, dtype=np.uint64) for _ in range(3))
+            _check(L.cc_size_filter(self._h, _ptr(labels), _ptr(out), labels.numel(), sel, value, _ptr(dis),
+                                    0 if dis is None else len(dis), 1 if relabel else 0, ctypes.byref(res),
+                                    _ptr(ids), _ptr(counts), _ptr(new), cap))
+            if int(res.n_unique) <= cap:
+                break
+            cap = int(res.n_unique)
+        n = int(res.n_unique)
+        ids, counts, new = ids[:n].copy(), counts[:n].copy(), new[:n].copy()
+        info = res.as_dict()
+        kept = new != 0                                # kept non-zero ids (their output value is >= 1)
+        table = np.stack([ids[kept], new[kept]], axis=1)
+        if n and info['start_label'] == 0:             # 0 occurs in the filtered volume: 0 -> 0 leads
+            table = np.concatenate([np.zeros((1, 2), dtype=np.uint64), table])
+        gone = ~kept
+        if n and ids[0] == 0:                          # id 0 (output 0 either way): by the counters
+            gone[0] = info['n_discarded'] > n - 1 - int(kept.sum())
+        info.update(ids=ids, counts=counts, new_ids=new, discard_ids=ids[gone], assignments=table)
+        return out, info
 
     def block_values(self, n_blocks):
         a = np.empty(n_blocks, dtype=np.uint64)

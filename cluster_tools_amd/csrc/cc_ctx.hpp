@@ -1,5 +1,5 @@
 // cc_ctx.hpp -- the host side shared by both translation units of libcc_mi355x.so (cc_lib.hip:
-// the labelling path; cc_aux.hip: evaluation, relabelling, prefilter, watershed): the context,
+// the labelling path; cc_aux.hip: evaluation, relabelling, size filter, prefilter, watershed): the context,
 // device memory (Arena / DevBuf), launches with optional event timing, synchronisation and
 // read-backs, the C-ABI error convention (CC_TRY).  Two units, so that the labelling path's
 // code object holds only its own kernels: the first launch from a code object loads all of its
@@ -255,6 +255,7 @@ struct cc_ctx {
         flags, map_ids, map_ids2, map_vals, map_par, big, pairsl, pc, ipairs, ipc, iovf, spec, mark, bflag,
         ev_main, ev_z, ev_seg, ev_gt, ev_flag, ev_part,   // evaluation (cc_eval.hip)
         rl_wg,                                            // relabel: per-workgroup id lists
+        sf_tab, sf_comp, sf_sorted, sf_list,              // size filter (cc_size_filter.hip)
         gs1, gs2, gs_tab,                                 // Gaussian prefilter temporaries (cc_prefilter.hip)
         mask_xmap,                                        // resized masks (cc_mask.hip)
         mlive,                                            // masked runs: blocks holding a mask voxel (k_mask_live)
@@ -262,6 +263,7 @@ struct cc_ctx {
         ws_tab, ws_buf;                                   // seeded watershed (cc_watershed.hip)
     int64_t ev_cap = 0;      // entries per evaluation hash table of the last cc_evaluate
     int64_t rl_cap = 0;      // id-set slots of the last cc_relabel_consecutive
+    int64_t sf_cap = 0;      // count-table slots of the last cc_label_sizes / cc_size_filter
     // last run
     int64_t n_blocks = 0;
     uint64_t n_labels = 0;
@@ -300,7 +302,7 @@ static inline std::vector<DevBuf*> ctx_bufs(cc_ctx* c) {
             &c->cub_tmp, &c->scalars, &c->counter, &c->in_tmp, &c->mask_tmp, &c->out_tmp, &c->pairs, &c->pairs2,
             &c->scalars2, &c->flags, &c->map_ids, &c->map_ids2, &c->map_vals, &c->map_par, &c->big, &c->pairsl, &c->pc,
             &c->ipairs, &c->ipc, &c->iovf, &c->spec, &c->mark, &c->bflag, &c->ev_main, &c->ev_z, &c->ev_seg, &c->ev_gt,
-            &c->ev_flag, &c->ev_part, &c->rl_wg, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
+            &c->ev_flag, &c->ev_part, &c->rl_wg, &c->sf_tab, &c->sf_comp, &c->sf_sorted, &c->sf_list, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
             &c->ws_buf, &c->status, &c->hmap_keys, &c->hmap_par};
 }
 

@@ -368,6 +368,51 @@ int64_t cc_get_overlaps(cc_ctx* ctx, uint64_t* seg_ids, uint64_t* gt_ids, uint64
 int cc_relabel_consecutive(cc_ctx* ctx, const uint64_t* labels_dev, uint64_t* out_dev, int64_t n,
                            uint64_t* n_unique, uint64_t* start_label, uint64_t* uniques_host, int64_t cap);
 
+/* --- per-id voxel counts and the size filter ------------------------------------
+ * FindUniques(return_counts) (relabel/find_uniques.py:105-179) over the whole volume: the sorted
+ * distinct ids of labels_dev (n uint64 device elements) and their voxel counts (np.unique with
+ * return_counts).  ids_host / counts_host (nullable, cap entries each): if one is given and
+ * cap < n_unique, only n_unique is returned and neither is written (call again with
+ * cap >= n_unique).  Id 2^64-1 is reserved (error). */
+int cc_label_sizes(cc_ctx* ctx, const uint64_t* labels_dev, int64_t n, uint64_t* n_unique,
+                   uint64_t* ids_host, uint64_t* counts_host, int64_t cap);
+
+/* SizeFilterWorkflow (postprocess/postprocess_workflow.py:24-110) in two passes over the volume:
+ * count, then one write pass that filters and (optionally) relabels.  Which ids are discarded is
+ * one of three selections:
+ *   CC_SF_SIZE_THRESHOLD  value = t: ids with count < t (size_filter_blocks.py:112; id 0 is
+ *                         counted like any id, discarding it changes nothing);
+ *   CC_SF_TARGET_NUMBER   value = k: all but the k ids with the largest counts
+ *                         (size_filter_blocks.py:116-117; id 0 competes like any id); among
+ *                         equal counts the larger id ranks first;
+ *   CC_SF_DISCARD_IDS     the n_discard ids of discard_host (ids that do not occur are ignored,
+ *                         duplicates allowed), as the BackgroundSizeFilter job reads them.
+ * value is ignored by CC_SF_DISCARD_IDS, discard_host / n_discard by the other two.
+ * Output (out_dev, may alias labels_dev): discarded ids become 0 (background_size_filter.py:
+ * 121-129); relabel = 0: kept ids stay; relabel = 1: the output is also relabelled consecutively
+ * as find_labeling.py:106-116 would relabel the filtered volume -- its sorted ids get
+ * start_label, start_label + 1, ... with start_label = 0 when 0 occurs in the filtered volume
+ * (it occurred in the input, or an occurring id was discarded), else 1.
+ * ids_host / counts_host / new_ids_host (nullable, cap entries each): the sorted distinct input
+ * ids, their counts, and the output value of each (0 for a discarded id).  If one is given and
+ * cap < n_unique, only result->n_unique is returned and out_dev is NOT written (safe for
+ * in-place calls: call again with cap >= n_unique).  Id 2^64-1 is reserved (error). */
+#define CC_SF_SIZE_THRESHOLD 0
+#define CC_SF_TARGET_NUMBER 1
+#define CC_SF_DISCARD_IDS 2
+typedef struct {
+    uint64_t n_unique;            /* distinct ids of the input                              */
+    uint64_t n_discarded;         /* occurring ids selected for discarding (0 included)     */
+    uint64_t n_kept;              /* n_unique - n_discarded                                 */
+    uint64_t start_label;         /* 0 when 0 occurs in the output, else 1                  */
+    uint64_t max_id;              /* largest id of the output                               */
+    uint64_t n_voxels_discarded;  /* voxels of discarded non-zero ids (those that changed)  */
+} cc_size_filter_result;
+int cc_size_filter(cc_ctx* ctx, const uint64_t* labels_dev, uint64_t* out_dev, int64_t n, int selection,
+                   uint64_t value, const uint64_t* discard_host, int64_t n_discard, int relabel,
+                   cc_size_filter_result* result, uint64_t* ids_host, uint64_t* counts_host,
+                   uint64_t* new_ids_host, int64_t cap);
+
 /* Seeded watershed per block (watershed/watershed_from_seeds.py:143-273, the WatershedFromSeeds
  * task of ThresholdAndWatershedWorkflow, thresholded_components_workflow.py:107-144): the seeds
  * (uint64 ids < 2^32 - 1, 0 = none; e.g. the thresholded components) grow over the input
