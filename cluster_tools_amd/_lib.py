@@ -30,7 +30,7 @@ EXPORTS = (
     'cc_watershed_from_seeds', 'cc_shard_dev_begin', 'cc_shard_dev_assign', 'cc_shard_dev_top_cubes',
     'cc_shard_dev_seam_pairs', 'cc_shard_dev_finish', 'cc_normalize_channels', 'cc_shard_dev_ok',
     'cc_comm_unique_id', 'cc_comm_create', 'cc_comm_destroy', 'cc_label_volume_sharded', 'cc_comm_info',
-    'cc_label_sizes', 'cc_size_filter',
+    'cc_label_sizes', 'cc_size_filter', 'cc_morphology',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -157,6 +157,7 @@ def load(host_only=False):
         'cc_relabel_consecutive': (I, [P, P, P, i64, P, P, P, i64]),
         'cc_label_sizes': (I, [P, P, i64, P, P, P, i64]),
         'cc_size_filter': (I, [P, P, P, i64, I, u64, P, i64, I, ctypes.POINTER(CCSizeFilterResult), P, P, P, i64]),
+        'cc_morphology': (I, [P, P, P, P, P, P, i64]),
         'cc_channel_mean': (I, [P, P, I, P, P, i64, P]),
         'cc_gaussian_smooth_blocks': (I, [P, P, P, P, ctypes.c_double, P]),
         'cc_gaussian_taps': (I, [ctypes.c_double, P, I]),
@@ -258,6 +259,63 @@ def mode_id(mode):
     if mode not in MODES:
         raise ValueError('threshold_mode must be one of %s' % (tuple(MODES),))
     return MODES[mode]
+
+
+# columns of a morphology table (block_morphology.py:128-133): id, size, centre of mass (z, y, x),
+# bounding-box minimum (z, y, x), inclusive maximum (z, y, x); a raw table (cc_morphology) holds
+# the coordinate sums in place of the centre
+MORPHOLOGY_COLUMNS = 11
+
+
+def _morphology_float(raw):
+    table = raw.astype(np.float64)
+    if len(raw):
+        table[:, 2:5] = raw[:, 2:5].astype(np.float64) / raw[:, 1:2].astype(np.float64)
+    return table
+
+
+def merge_morphology(raw_tables):
+    """The raw (n_i, 11) uint64 tables (Context.morphology(raw=True)) of disjoint pieces of one
+    volume, each computed with its piece's origin, merged exactly into the raw table of the whole:
+    per id the sizes and coordinate sums add, the minima take the min, the maxima the max; sorted
+    by id."""
+    tables = [np.asarray(t, dtype=np.uint64).reshape(-1, MORPHOLOGY_COLUMNS) for t in raw_tables]
+    rows = np.concatenate(tables) if tables else np.zeros((0, MORPHOLOGY_COLUMNS), dtype=np.uint64)
+    ids, inv = np.unique(rows[:, 0], return_inverse=True)
+    inv = inv.reshape(-1)
+    out = np.zeros((len(ids), MORPHOLOGY_COLUMNS), dtype=np.uint64)
+    out[:, 0] = ids
+    out[:, 5:8] = np.iinfo(np.uint64).max
+    np.add.at(out[:, 1:5], inv, rows[:, 1:5])
+    np.minimum.at(out[:, 5:8], inv, rows[:, 5:8])
+    np.maximum.at(out[:, 8:11], inv, rows[:, 8:11])
+    return out
+
+
+def morphology_table(raw, number_of_labels):
+    """The dense (number_of_labels, 11) float64 table the reference's MergeMorphology writes
+    (merge_morphology.py:48-56), from a raw table: row i is id i, columns 2:5 the centre of mass
+    float64(sum) / float64(size).  An id that does not occur gets column 0 = i and zeros
+    elsewhere; what nifty's mergeAndSerializeMorphology writes for absent ids could not be checked
+    (nifty is not available), so those rows are this project's choice.  An occurring id >=
+    number_of_labels raises ValueError."""
+    return morphology_table_rows(raw, number_of_labels, 0, int(number_of_labels))
+
+
+def morphology_table_rows(raw, number_of_labels, id_begin, id_end):
+    """Rows id_begin .. id_end - 1 of morphology_table(raw, number_of_labels) (one id chunk of
+    the MergeMorphology job); raw is sorted by id."""
+    raw = np.asarray(raw, dtype=np.uint64).reshape(-1, MORPHOLOGY_COLUMNS)
+    number_of_labels, id_begin, id_end = int(number_of_labels), int(id_begin), int(id_end)
+    assert 0 <= id_begin <= id_end <= number_of_labels
+    if len(raw) and int(raw[:, 0].max()) >= number_of_labels:
+        raise ValueError('label id %d does not fit a table of %d labels (number_of_labels = maxId + 1)'
+                         % (int(raw[:, 0].max()), number_of_labels))
+    lo, hi = np.searchsorted(raw[:, 0], np.array([id_begin, id_end], dtype=np.uint64))
+    table = np.zeros((id_end - id_begin, MORPHOLOGY_COLUMNS), dtype=np.float64)
+    table[:, 0] = np.arange(id_begin, id_end, dtype=np.float64)
+    table[raw[lo:hi, 0].astype(np.int64) - id_begin] = _morphology_float(raw[lo:hi])
+    return table
 
 
 def comm_unique_id():
@@ -642,6 +700,32 @@ class Context:
             cap = int(nu[0])
         n = int(nu[0])
         return ids[:n].copy(), counts[:n].copy()
+
+    def morphology(self, labels, origin=(0, 0, 0), cap_hint=1 << 20, raw=False):
+        """MorphologyWorkflow (morphology/morphology_workflow.py:11-56) over the whole volume on
+        device, in one read pass: one row per distinct id of the contiguous 3-D uint64 (torch int64 /
+        uint64) CUDA tensor `labels`, sorted by id (id 0 included), with the reference's columns
+        id, size, centre of mass (z, y, x), bounding-box minimum (z, y, x) and inclusive maximum
+        (z, y, x).  origin: where `labels` starts in the volume it is a piece of (coordinates are
+        origin + position).  raw=True: the exact (n, 11) uint64 rows of cc_morphology, with the
+        coordinate sums in columns 2:5 (what merge_morphology adds up); otherwise the (n, 11)
+        float64 table, columns 2:5 = float64(sum) / float64(size).  cap_hint: the expected number
+        of distinct ids (a larger count costs a second call)."""
+        self._check_labels(labels)
+        assert labels.dim() == 3, 'labels must be 3-D (z, y, x)'
+        shape, org = _i64(labels.shape), _i64(origin)
+        assert org.shape == (3,)
+        L = load()
+        nu = np.zeros(1, dtype=np.uint64)
+        cap = max(1, int(cap_hint))
+        while True:
+            rows = np.empty((cap, MORPHOLOGY_COLUMNS), dtype=np.uint64)
+            _check(L.cc_morphology(self._h, _ptr(labels), _ptr(shape), _ptr(org), _ptr(nu), _ptr(rows), cap))
+            if int(nu[0]) <= cap:
+                break
+            cap = int(nu[0])
+        rows = rows[:int(nu[0])].copy()
+        return rows if raw else _morphology_float(rows)
 
     def size_filter(self, labels, size_threshold=None, target_number=None, discard_ids=None, relabel=True,
                     out=None, cap_hint=1 << 20):

@@ -256,6 +256,7 @@ struct cc_ctx {
         ev_main, ev_z, ev_seg, ev_gt, ev_flag, ev_part,   // evaluation (cc_eval.hip)
         rl_wg,                                            // relabel: per-workgroup id lists
         sf_tab, sf_comp, sf_sorted, sf_list,              // size filter (cc_size_filter.hip)
+        mo_tab, mo_rows,                                  // morphology table and its sorted rows (cc_morphology.hip)
         gs1, gs2, gs_tab,                                 // Gaussian prefilter temporaries (cc_prefilter.hip)
         mask_xmap,                                        // resized masks (cc_mask.hip)
         mlive,                                            // masked runs: blocks holding a mask voxel (k_mask_live)
@@ -264,6 +265,7 @@ struct cc_ctx {
     int64_t ev_cap = 0;      // entries per evaluation hash table of the last cc_evaluate
     int64_t rl_cap = 0;      // id-set slots of the last cc_relabel_consecutive
     int64_t sf_cap = 0;      // count-table slots of the last cc_label_sizes / cc_size_filter
+    int64_t mo_cap = 0;      // table slots of the last cc_morphology
     // last run
     int64_t n_blocks = 0;
     uint64_t n_labels = 0;
@@ -302,7 +304,7 @@ static inline std::vector<DevBuf*> ctx_bufs(cc_ctx* c) {
             &c->cub_tmp, &c->scalars, &c->counter, &c->in_tmp, &c->mask_tmp, &c->out_tmp, &c->pairs, &c->pairs2,
             &c->scalars2, &c->flags, &c->map_ids, &c->map_ids2, &c->map_vals, &c->map_par, &c->big, &c->pairsl, &c->pc,
             &c->ipairs, &c->ipc, &c->iovf, &c->spec, &c->mark, &c->bflag, &c->ev_main, &c->ev_z, &c->ev_seg, &c->ev_gt,
-            &c->ev_flag, &c->ev_part, &c->rl_wg, &c->sf_tab, &c->sf_comp, &c->sf_sorted, &c->sf_list, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
+            &c->ev_flag, &c->ev_part, &c->rl_wg, &c->sf_tab, &c->sf_comp, &c->sf_sorted, &c->sf_list, &c->mo_tab, &c->mo_rows, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
             &c->ws_buf, &c->status, &c->hmap_keys, &c->hmap_par};
 }
 

@@ -413,6 +413,21 @@ int cc_size_filter(cc_ctx* ctx, const uint64_t* labels_dev, uint64_t* out_dev, i
                    cc_size_filter_result* result, uint64_t* ids_host, uint64_t* counts_host,
                    uint64_t* new_ids_host, int64_t cap);
 
+/* --- per-id morphology table -----------------------------------------------------
+ * MorphologyWorkflow (morphology/morphology_workflow.py:11-56; block_morphology.py:128-136,
+ * merge_morphology.py:125-132) over the whole volume in one read pass: labels_dev holds
+ * shape[0] x shape[1] x shape[2] (z, y, x) uint64 device elements, the piece of a larger volume
+ * that starts at origin.
+ * one row per distinct id, sorted by id, 11 uint64 in the column order of the reference's table:
+ * id, size, sum_z, sum_y, sum_x, min_z, min_y, min_x, max_z, max_y, max_x  (max inclusive;
+ * coordinates are global: origin + position in labels_dev; the centre of mass is sum / size).
+ * Id 0 is an id like any other.  rows_host (nullable, cap x 11): if cap < n_unique, only n_unique
+ * is returned and nothing is written (call again with cap >= n_unique).  Every dimension and
+ * origin + shape must be below 2^31, and voxels x max(origin + shape) below 2^64 (the sums are
+ * exact).  A shape with a zero dimension gives n_unique = 0.  Id 2^64-1 is reserved (error). */
+int cc_morphology(cc_ctx* ctx, const uint64_t* labels_dev, const int64_t shape[3], const int64_t origin[3],
+                  uint64_t* n_unique, uint64_t* rows_host /* cap x 11, nullable */, int64_t cap);
+
 /* Seeded watershed per block (watershed/watershed_from_seeds.py:143-273, the WatershedFromSeeds
  * task of ThresholdAndWatershedWorkflow, thresholded_components_workflow.py:107-144): the seeds
  * (uint64 ids < 2^32 - 1, 0 = none; e.g. the thresholded components) grow over the input
