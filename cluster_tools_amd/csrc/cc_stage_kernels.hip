@@ -230,9 +230,25 @@ __global__ void k_union_pairs(int64_t n, const u64* pairs, u64 n_labels, u64* P,
     }
 }
 
+// P[i] = root(i) for every i at once.  While thread i stores its root, other threads still walk
+// through i and halve paths: a halving store of an ancestor read earlier landing after the root's
+// store left P[i] at a non-root (a shuffled 100 k-id chain: a few ids per run).  A parent is always
+// smaller than its child (a root links to a smaller root) and the root is the smallest of all, so
+// here both stores are atomicMin: P[i] only ever moves towards the root.
+__device__ __forceinline__ u64 gfind64_min(u64* P, u64 x) {
+    while (true) {
+        u64 p = gload64(P + x);
+        if (p == x) return x;
+        u64 gp = gload64(P + p);
+        if (gp == p) return p;
+        atomicMin((unsigned long long*)(P + x), (unsigned long long)gp);
+        x = gp;
+    }
+}
+
 __global__ void k_resolve64(u64 n, u64* P) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) P[i] = gfind64(P, i);
+    if (i < n) atomicMin((unsigned long long*)(P + i), (unsigned long long)gfind64_min(P, i));
 }
 
 // write.py:185-202 -- per non-empty block seg[seg != 0] += off[block]; seg = lut[seg], in place.
