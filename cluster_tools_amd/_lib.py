@@ -30,7 +30,7 @@ EXPORTS = (
     'cc_watershed_from_seeds', 'cc_shard_dev_begin', 'cc_shard_dev_assign', 'cc_shard_dev_top_cubes',
     'cc_shard_dev_seam_pairs', 'cc_shard_dev_finish', 'cc_normalize_channels', 'cc_shard_dev_ok',
     'cc_comm_unique_id', 'cc_comm_create', 'cc_comm_destroy', 'cc_label_volume_sharded', 'cc_comm_info',
-    'cc_label_sizes', 'cc_size_filter', 'cc_morphology',
+    'cc_label_sizes', 'cc_size_filter', 'cc_morphology', 'cc_region_features',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -158,6 +158,7 @@ def load(host_only=False):
         'cc_label_sizes': (I, [P, P, i64, P, P, P, i64]),
         'cc_size_filter': (I, [P, P, P, i64, I, u64, P, i64, I, ctypes.POINTER(CCSizeFilterResult), P, P, P, i64]),
         'cc_morphology': (I, [P, P, P, P, P, P, i64]),
+        'cc_region_features': (I, [P, P, P, I, i64, P, P, P, P, P, P, i64]),
         'cc_channel_mean': (I, [P, P, I, P, P, i64, P]),
         'cc_gaussian_smooth_blocks': (I, [P, P, P, P, ctypes.c_double, P]),
         'cc_gaussian_taps': (I, [ctypes.c_double, P, I]),
@@ -315,6 +316,98 @@ def morphology_table_rows(raw, number_of_labels, id_begin, id_end):
     table = np.zeros((id_end - id_begin, MORPHOLOGY_COLUMNS), dtype=np.float64)
     table[:, 0] = np.arange(id_begin, id_end, dtype=np.float64)
     table[raw[lo:hi, 0].astype(np.int64) - id_begin] = _morphology_float(raw[lo:hi])
+    return table
+
+# features of a region features table (features/region_features.py:215-217; the reference runs
+# with count and mean only); a raw table (cc_region_features) is a dict of the arrays RAW_REGION_FEATURES
+REGION_FEATURES = ('count', 'mean', 'minimum', 'maximum')
+RAW_REGION_FEATURES = (('ids', np.uint64), ('count', np.uint64), ('sum', np.float64), ('minimum', np.float32),
+                       ('maximum', np.float32))
+
+
+def _raw_region_features(raw):
+    return {k: np.asarray(raw[k], dtype=t).reshape(-1) for k, t in RAW_REGION_FEATURES}
+
+
+def _region_features_float(raw, uint8_input):
+    """(n, 5) float64 [id, count, mean, minimum, maximum] of a raw table; uint8 input: mean,
+    minimum and maximum / 255 (the reference's normalize(x, 0, 255), once per id)."""
+    raw = _raw_region_features(raw)
+    table = np.zeros((len(raw['ids']), 5), dtype=np.float64)
+    table[:, 0] = raw['ids'].astype(np.float64)
+    table[:, 1] = raw['count'].astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        table[:, 2] = raw['sum'] / table[:, 1]
+    table[:, 3] = raw['minimum'].astype(np.float64)
+    table[:, 4] = raw['maximum'].astype(np.float64)
+    if uint8_input:
+        table[:, 2:] /= 255.
+    return table
+
+
+def merge_region_features(raw_tables):
+    """The raw tables (Context.region_features(raw=True)) of disjoint pieces of one volume merged
+    into the raw table of the whole: per id the counts and the sums add (float64, in the order of
+    the pieces: exact for uint8 and other inputs whose partial sums are representable), the minima
+    take the min and the maxima the max (a NaN stays); sorted by id."""
+    tables = [_raw_region_features(t) for t in raw_tables]
+    cat = {k: (np.concatenate([t[k] for t in tables]) if tables else np.zeros(0, dtype=d)) for k, d in RAW_REGION_FEATURES}
+    ids, inv = np.unique(cat['ids'], return_inverse=True)
+    inv = inv.reshape(-1)
+    out = {'ids': ids, 'count': np.zeros(len(ids), dtype=np.uint64), 'sum': np.zeros(len(ids), dtype=np.float64),
+           'minimum': np.full(len(ids), np.inf, dtype=np.float32), 'maximum': np.full(len(ids), -np.inf, dtype=np.float32)}
+    np.add.at(out['count'], inv, cat['count'])
+    # np.minimum / np.maximum propagate a NaN; among equal zeros -0 is the minimum, +0 the maximum
+    with np.errstate(invalid='ignore'):
+        np.add.at(out['sum'], inv, cat['sum'])
+        np.minimum.at(out['minimum'], inv, cat['minimum'])
+        np.maximum.at(out['maximum'], inv, cat['maximum'])
+    neg0 = (cat['minimum'] == 0) & np.signbit(cat['minimum'])
+    hit = np.zeros(len(ids), dtype=bool)
+    hit[inv[neg0]] = True
+    out['minimum'][hit & (out['minimum'] == 0)] = np.float32(-0.0)
+    pos0 = (cat['maximum'] == 0) & ~np.signbit(cat['maximum'])
+    hit = np.zeros(len(ids), dtype=bool)
+    hit[inv[pos0]] = True
+    out['maximum'][hit & (out['maximum'] == 0)] = np.float32(0.0)
+    return out
+
+
+def region_features_table(raw, number_of_labels, feature_names=('count', 'mean'), ignore_label=0, uint8_input=False):
+    """The dense (number_of_labels, n_features) float32 table the reference's MergeRegionFeatures
+    writes (merge_region_features.py:116-165), from a raw table: row i is id i, the columns follow
+    feature_names (a subset of count, mean, minimum, maximum, count first as the reference asserts).
+    Ids that do not occur are all-zero rows, and so is the ignore_label row (what vigra's
+    ignoreLabel leaves; None keeps it).  uint8_input: mean, minimum and maximum / 255.  Computed in
+    float64 and rounded once to float32 (the count column is float32(count): inexact above 2^24,
+    the raw table is the exact one).  An occurring id >= number_of_labels raises ValueError."""
+    return region_features_table_rows(raw, number_of_labels, 0, int(number_of_labels), feature_names, ignore_label,
+                                      uint8_input)
+
+
+def region_features_table_rows(raw, number_of_labels, id_begin, id_end, feature_names=('count', 'mean'),
+                               ignore_label=0, uint8_input=False):
+    """Rows id_begin .. id_end - 1 of region_features_table (the id chunks of one
+    MergeRegionFeatures job); raw is sorted by id."""
+    feature_names = list(feature_names)
+    if not feature_names or feature_names[0] != 'count' or len(set(feature_names)) != len(feature_names) \
+            or any(name not in REGION_FEATURES for name in feature_names):
+        raise ValueError("feature_names must be a subset of %s that starts with 'count', got %s"
+                         % (REGION_FEATURES, feature_names))
+    raw = _raw_region_features(raw)
+    ids = raw['ids']
+    number_of_labels, id_begin, id_end = int(number_of_labels), int(id_begin), int(id_end)
+    assert 0 <= id_begin <= id_end <= number_of_labels
+    if len(ids) and int(ids.max()) >= number_of_labels:
+        raise ValueError('label id %d does not fit a table of %d labels (number_of_labels = maxId + 1)'
+                         % (int(ids.max()), number_of_labels))
+    lo, hi = np.searchsorted(ids, np.array([id_begin, id_end], dtype=np.uint64))
+    rows = _region_features_float({k: v[lo:hi] for k, v in raw.items()}, uint8_input)
+    cols = [1 + REGION_FEATURES.index(name) for name in feature_names]
+    table = np.zeros((id_end - id_begin, len(cols)), dtype=np.float32)
+    table[ids[lo:hi].astype(np.int64) - id_begin] = rows[:, cols].astype(np.float32)
+    if ignore_label is not None and id_begin <= int(ignore_label) < id_end:
+        table[int(ignore_label) - id_begin] = 0
     return table
 
 
@@ -726,6 +819,41 @@ class Context:
             cap = int(nu[0])
         rows = rows[:int(nu[0])].copy()
         return rows if raw else _morphology_float(rows)
+
+    def region_features(self, labels, values, cap_hint=1 << 20, raw=False):
+        """RegionFeaturesWorkflow (features/region_features.py:140-192, merge_region_features.py:
+        116-165) over the whole volume on device, in one read pass over both operands: one entry
+        per distinct id of the contiguous uint64 (torch int64 / uint64) CUDA tensor `labels`, sorted
+        by id (id 0 included), over the values of the contiguous float32 or uint8 CUDA tensor
+        `values` with as many elements (element i is the value of voxel i).  raw=True: the exact
+        device results, a dict of numpy arrays ids (u64), count (u64), sum (f64: each value
+        converted exactly, uint8 as its integer), minimum and maximum (f32) -- what
+        merge_region_features merges.  Otherwise the (n, 5) float64 table [id, count, mean,
+        minimum, maximum] with mean = sum / count; for uint8 input mean, minimum and maximum are
+        / 255.  An id that holds a NaN has a NaN sum, minimum and maximum; no other id is
+        affected.  cap_hint: the expected number of distinct ids (a larger count costs a second
+        call)."""
+        import torch
+        self._check_labels(labels)
+        assert hasattr(values, 'data_ptr') and values.is_cuda and values.is_contiguous(), \
+            'values must be a contiguous CUDA tensor'
+        assert values.dtype in (torch.float32, torch.uint8), 'values must be float32 or uint8'
+        assert values.numel() == labels.numel(), 'labels and values must have the same number of elements'
+        assert values.device == labels.device
+        u8 = values.dtype == torch.uint8
+        L = load()
+        nu = np.zeros(1, dtype=np.uint64)
+        cap = max(1, int(cap_hint))
+        while True:
+            out = {k: np.empty(cap, dtype=t) for k, t in RAW_REGION_FEATURES}
+            _check(L.cc_region_features(self._h, _ptr(labels), _ptr(values), 1 if u8 else 0, labels.numel(), _ptr(nu),
+                                        _ptr(out['ids']), _ptr(out['count']), _ptr(out['sum']), _ptr(out['minimum']),
+                                        _ptr(out['maximum']), cap))
+            if int(nu[0]) <= cap:
+                break
+            cap = int(nu[0])
+        out = {k: v[:int(nu[0])].copy() for k, v in out.items()}
+        return out if raw else _region_features_float(out, u8)
 
     def size_filter(self, labels, size_threshold=None, target_number=None, discard_ids=None, relabel=True,
                     out=None, cap_hint=1 << 20):

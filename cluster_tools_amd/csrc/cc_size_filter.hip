@@ -19,13 +19,13 @@ namespace cc {
 // (same lane or the lane below; lane 0's first id always).  Unlike rl_heads the padding past the
 // end (2^64 - 1) is kept: its first id ends the last run.  nonempty: the ids that are not
 // 2^64 - 1; e_or |= EV_ERR_GT for a reserved id inside the range
-template <int VW>
+template <int VW, int Q = RL_Q>
 __device__ __forceinline__ u32 sf_bounds(const RlVec<VW>* x, int64_t base, int64_t end, int lane, u32& nonempty,
                                          u32& e_or) {
     u32 bm = 0;
     nonempty = 0;
 #pragma unroll
-    for (int q = 0; q < RL_Q; ++q) {
+    for (int q = 0; q < Q; ++q) {
         const int64_t i = base + (q * 64 + lane) * VW;
         const u64 prev = (u64)__shfl_up((unsigned long long)x[q].v[VW - 1], 1);
 #pragma unroll

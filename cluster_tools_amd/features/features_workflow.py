@@ -1,0 +1,52 @@
+"""RegionFeaturesWorkflow (reference: cluster_tools/features/features_workflow.py): the same
+parameters and task chain RegionFeatures -> MergeRegionFeatures, writing the (maxId + 1,
+n_features) float32 table of per-id intensity features (count and mean; minimum and maximum when
+the region_features task config asks for them) of an input volume over a label volume.
+number_of_labels = maxId + 1 is read from the label dataset's attributes in requires(), as the
+reference does, so the labels must have been written (with their maxId) before the workflow is
+instantiated into a task graph.  EdgeFeaturesWorkflow is not available.  target must be 'local'."""
+from cluster_tools_amd.luigi_compat import Parameter, IntParameter
+from cluster_tools_amd.cluster_tasks import WorkflowBase
+from cluster_tools_amd.utils import volume_utils as vu
+from cluster_tools_amd.features import region_features as feat_tasks
+from cluster_tools_amd.features import merge_region_features as merge_tasks
+
+
+class RegionFeaturesWorkflow(WorkflowBase):
+    input_path = Parameter()
+    input_key = Parameter()
+    labels_path = Parameter()
+    labels_key = Parameter()
+    output_path = Parameter()
+    output_key = Parameter()
+    prefix = Parameter(default='')
+    max_jobs_merge = IntParameter(default=None)
+    channel = IntParameter(default=None)
+
+    def read_number_of_labels(self):
+        with vu.file_reader(self.labels_path, 'r') as f:
+            max_id = f[self.labels_key].attrs.get('maxId', None)
+        if max_id is None:
+            raise ValueError("%s:%s has no 'maxId' attribute: the feature table has maxId + 1 rows (the "
+                             "connected-components and size-filter jobs write it)" % (self.labels_path, self.labels_key))
+        return int(max_id) + 1
+
+    def requires(self):
+        feat_task = getattr(feat_tasks, self._get_task_name('RegionFeatures'))
+        dep = feat_task(tmp_folder=self.tmp_folder, max_jobs=self.max_jobs, config_dir=self.config_dir,
+                        input_path=self.input_path, input_key=self.input_key, labels_path=self.labels_path,
+                        labels_key=self.labels_key, prefix=self.prefix, channel=self.channel,
+                        dependency=self.dependency)
+        merge_task = getattr(merge_tasks, self._get_task_name('MergeRegionFeatures'))
+        max_jobs_merge = self.max_jobs if self.max_jobs_merge is None else self.max_jobs_merge
+        dep = merge_task(tmp_folder=self.tmp_folder, max_jobs=max_jobs_merge, config_dir=self.config_dir,
+                         output_path=self.output_path, output_key=self.output_key,
+                         number_of_labels=self.read_number_of_labels(), prefix=self.prefix, dependency=dep)
+        return dep
+
+    @staticmethod
+    def get_config():
+        configs = WorkflowBase.get_config()
+        configs.update({'region_features': feat_tasks.RegionFeaturesLocal.default_task_config(),
+                        'merge_region_features': merge_tasks.MergeRegionFeaturesLocal.default_task_config()})
+        return configs

@@ -428,6 +428,26 @@ int cc_size_filter(cc_ctx* ctx, const uint64_t* labels_dev, uint64_t* out_dev, i
 int cc_morphology(cc_ctx* ctx, const uint64_t* labels_dev, const int64_t shape[3], const int64_t origin[3],
                   uint64_t* n_unique, uint64_t* rows_host /* cap x 11, nullable */, int64_t cap);
 
+/* --- per-id intensity features ---------------------------------------------------
+ * RegionFeaturesWorkflow (features/region_features.py:140-192, merge_region_features.py:116-165)
+ * over the whole volume in one read pass: labels_dev holds n uint64 device elements (flat, no
+ * coordinates), values_dev n values of value_type (CC_RF_FLOAT32 or CC_RF_UINT8), element i the
+ * value of voxel i.  One entry per distinct id, sorted by id, id 0 included:
+ *   ids, counts (exact), sums (float64 sum of the id's values, each converted exactly -- float32
+ *   as it is, uint8 as its integer, no / 255; the uint8 sum is an exact integer, the float32 sum
+ *   is added in an order that varies from call to call, every add inside the id's own values: its
+ *   error is at most gamma(count - 1) sum|x| of that id alone), mins / maxs (float32, exact).
+ * IEEE rules hold for the sums (an infinity propagates, a NaN makes its id's sum NaN).  An id that
+ * holds a NaN has minimum = maximum = NaN; -0 orders below +0.  No id is affected by another
+ * id's values.  The host arrays are nullable, cap entries each: if one is given and cap <
+ * n_unique, only n_unique is returned and nothing is written (call again with cap >= n_unique).
+ * Neither input is modified.  n = 0 gives n_unique = 0.  Id 2^64-1 is reserved (error). */
+#define CC_RF_FLOAT32 0
+#define CC_RF_UINT8 1
+int cc_region_features(cc_ctx* ctx, const uint64_t* labels_dev, const void* values_dev, int value_type, int64_t n,
+                       uint64_t* n_unique, uint64_t* ids_host, uint64_t* counts_host, double* sums_host,
+                       float* mins_host, float* maxs_host, int64_t cap);
+
 /* Seeded watershed per block (watershed/watershed_from_seeds.py:143-273, the WatershedFromSeeds
  * task of ThresholdAndWatershedWorkflow, thresholded_components_workflow.py:107-144): the seeds
  * (uint64 ids < 2^32 - 1, 0 = none; e.g. the thresholded components) grow over the input
