@@ -31,10 +31,11 @@ EXPORTS = (
     'cc_shard_dev_seam_pairs', 'cc_shard_dev_finish', 'cc_normalize_channels', 'cc_shard_dev_ok',
     'cc_comm_unique_id', 'cc_comm_create', 'cc_comm_destroy', 'cc_label_volume_sharded', 'cc_comm_info',
     'cc_label_sizes', 'cc_size_filter', 'cc_morphology', 'cc_region_features',
+    'cc_region_graph',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
-CC_ERR_ID_RANGE = -3          # cc_evaluate: ids beyond the key packing (include/cc_mi355x.h)
+CC_ERR_ID_RANGE = -3          # cc_evaluate, cc_region_graph: ids beyond the key packing (include/cc_mi355x.h)
 # CC_DTYPE_* of include/cc_mi355x.h (cc_channel_mean)
 DTYPES = {'float32': 0, 'float64': 1, 'uint8': 2, 'int8': 3, 'uint16': 4, 'int16': 5, 'uint32': 6,
           'int32': 7, 'uint64': 8, 'int64': 9}
@@ -159,6 +160,7 @@ def load(host_only=False):
         'cc_size_filter': (I, [P, P, P, i64, I, u64, P, i64, I, ctypes.POINTER(CCSizeFilterResult), P, P, P, i64]),
         'cc_morphology': (I, [P, P, P, P, P, P, i64]),
         'cc_region_features': (I, [P, P, P, I, i64, P, P, P, P, P, P, i64]),
+        'cc_region_graph': (I, [P, P, P, P, I, P, P, i64, P, P, P, i64]),
         'cc_channel_mean': (I, [P, P, I, P, P, i64, P]),
         'cc_gaussian_smooth_blocks': (I, [P, P, P, P, ctypes.c_double, P]),
         'cc_gaussian_taps': (I, [ctypes.c_double, P, I]),
@@ -409,6 +411,33 @@ def region_features_table_rows(raw, number_of_labels, id_begin, id_end, feature_
     if ignore_label is not None and id_begin <= int(ignore_label) < id_end:
         table[int(ignore_label) - id_begin] = 0
     return table
+
+
+def _region_graph(table):
+    return {'nodes': np.asarray(table['nodes'], dtype=np.uint64).reshape(-1),
+            'edges': np.asarray(table['edges'], dtype=np.uint64).reshape(-1, 2),
+            'sizes': np.asarray(table['sizes'], dtype=np.uint64).reshape(-1)}
+
+
+def merge_region_graphs(tables):
+    """The graphs (Context.region_graph) of the pieces of one volume, each computed on its piece
+    plus a one-plane halo on the upper side of every axis with `owned` = the piece's own extent,
+    merged into the graph of the whole: the union of the nodes, the union of the edges with the
+    sizes of equal edges added; nodes sorted, edges sorted by (u, v).  Every voxel face of the
+    volume has its lower-coordinate voxel in exactly one piece, so the sizes add up exactly."""
+    tables = [_region_graph(t) for t in tables]
+    if not tables:
+        tables = [{'nodes': np.zeros(0, np.uint64), 'edges': np.zeros((0, 2), np.uint64), 'sizes': np.zeros(0, np.uint64)}]
+    nodes = np.unique(np.concatenate([t['nodes'] for t in tables]))
+    edges = np.concatenate([t['edges'] for t in tables])
+    sizes = np.concatenate([t['sizes'] for t in tables])
+    assert len(edges) == len(sizes)
+    if len(edges):
+        order = np.lexsort((edges[:, 1], edges[:, 0]))
+        edges, sizes = edges[order], sizes[order]
+        first = np.flatnonzero(np.concatenate([[True], (edges[1:] != edges[:-1]).any(axis=1)]))
+        edges, sizes = edges[first], np.add.reduceat(sizes, first)
+    return {'nodes': nodes, 'edges': np.ascontiguousarray(edges), 'sizes': sizes.astype(np.uint64)}
 
 
 def comm_unique_id():
@@ -854,6 +883,59 @@ class Context:
             cap = int(nu[0])
         out = {k: v[:int(nu[0])].copy() for k, v in out.items()}
         return out if raw else _region_features_float(out, u8)
+
+    def region_graph(self, labels, ignore_label=True, owned=None, cap_hint=1 << 20):
+        """GraphWorkflow (graph/graph_workflow.py:9-74) over the whole volume on device, in one
+        read pass: the region adjacency graph of the contiguous 3-D uint64 (torch int64 / uint64)
+        CUDA tensor `labels` as a dict of uint64 numpy arrays: nodes (n,), the sorted distinct ids;
+        edges (m, 2), the pairs (u, v), u < v, of ids that meet across a voxel face of the
+        6-neighbourhood, sorted by (u, v); sizes (m,), the number of faces per edge.
+        ignore_label=True (the reference's task default): faces with a 0 on either side make no
+        edge and 0 is no node.  owned (oz, oy, ox) <= labels.shape: `labels` is a piece of a larger
+        volume with a read-only halo beyond the owned box; a face counts when its lower-coordinate
+        voxel lies in the owned box, an id is a node when it occurs there (merge_region_graphs
+        merges such pieces).  cap_hint: the expected number of nodes and of edges (larger counts
+        cost a second call).
+
+        The device table packs an edge into one 64-bit key (ids < 2^32 - 1).  Volumes with larger
+        ids are first relabelled consecutively on the device (relabel_consecutive: order-preserving,
+        0 stays 0) and the nodes and edges are mapped back; the map is monotone, so they stay
+        sorted."""
+        self._check_labels(labels)
+        assert labels.dim() == 3, 'labels must be 3-D (z, y, x)'
+        shape = _i64(labels.shape)
+        own = shape if owned is None else _i64(owned)
+        assert own.shape == (3,) and (own >= 0).all() and (own <= shape).all(), 'owned must lie within labels.shape'
+        L = load()
+
+        def call(lab):
+            nn, ne = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+            ncap = ecap = max(1, int(cap_hint))
+            while True:
+                nodes, edges, sizes = (np.empty(ncap, dtype=np.uint64), np.empty((ecap, 2), dtype=np.uint64),
+                                       np.empty(ecap, dtype=np.uint64))
+                rc = L.cc_region_graph(self._h, _ptr(lab), _ptr(shape), _ptr(own), int(bool(ignore_label)), _ptr(nn),
+                                       _ptr(nodes), ncap, _ptr(ne), _ptr(edges), _ptr(sizes), ecap)
+                if rc != 0:
+                    return rc, None
+                if int(nn[0]) <= ncap and int(ne[0]) <= ecap:
+                    break
+                ncap, ecap = max(ncap, int(nn[0])), max(ecap, int(ne[0]))
+            n, m = int(nn[0]), int(ne[0])
+            return 0, {'nodes': nodes[:n].copy(), 'edges': edges[:m].copy(), 'sizes': sizes[:m].copy()}
+
+        rc, graph = call(labels)
+        if rc == 0:
+            return graph
+        if rc != CC_ERR_ID_RANGE:                      # CC_ERR_ID_RANGE: relabel and call again
+            _check(rc)
+        relabelled, table = self.relabel_consecutive(labels)
+        rc, graph = call(relabelled)
+        _check(rc)
+        first = table[0, 1] if len(table) else np.uint64(0)
+        for k in ('nodes', 'edges'):                   # back from the relabelled id space
+            graph[k] = table[(graph[k] - first).astype(np.int64), 0]
+        return graph
 
     def size_filter(self, labels, size_threshold=None, target_number=None, discard_ids=None, relabel=True,
                     out=None, cap_hint=1 << 20):

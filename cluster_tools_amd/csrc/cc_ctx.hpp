@@ -258,6 +258,7 @@ struct cc_ctx {
         sf_tab, sf_comp, sf_sorted, sf_list,              // size filter (cc_size_filter.hip)
         mo_tab, mo_rows,                                  // morphology table and its sorted rows (cc_morphology.hip)
         rf_tab, rf_rows,                                  // region features table and its sorted entries (cc_region_features.hip)
+        gr_tab, gr_comp, gr_sorted,                       // region graph: table, compacted and sorted entries (cc_graph.hip)
         gs1, gs2, gs_tab,                                 // Gaussian prefilter temporaries (cc_prefilter.hip)
         mask_xmap,                                        // resized masks (cc_mask.hip)
         mlive,                                            // masked runs: blocks holding a mask voxel (k_mask_live)
@@ -268,6 +269,7 @@ struct cc_ctx {
     int64_t sf_cap = 0;      // count-table slots of the last cc_label_sizes / cc_size_filter
     int64_t mo_cap = 0;      // table slots of the last cc_morphology
     int64_t rf_cap = 0;      // table slots of the last cc_region_features
+    int64_t gr_cap = 0;      // table slots of the last cc_region_graph
     // last run
     int64_t n_blocks = 0;
     uint64_t n_labels = 0;
@@ -306,7 +308,8 @@ static inline std::vector<DevBuf*> ctx_bufs(cc_ctx* c) {
             &c->cub_tmp, &c->scalars, &c->counter, &c->in_tmp, &c->mask_tmp, &c->out_tmp, &c->pairs, &c->pairs2,
             &c->scalars2, &c->flags, &c->map_ids, &c->map_ids2, &c->map_vals, &c->map_par, &c->big, &c->pairsl, &c->pc,
             &c->ipairs, &c->ipc, &c->iovf, &c->spec, &c->mark, &c->bflag, &c->ev_main, &c->ev_z, &c->ev_seg, &c->ev_gt,
-            &c->ev_flag, &c->ev_part, &c->rl_wg, &c->sf_tab, &c->sf_comp, &c->sf_sorted, &c->sf_list, &c->mo_tab, &c->mo_rows, &c->rf_tab, &c->rf_rows, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
+            &c->ev_flag, &c->ev_part, &c->rl_wg, &c->sf_tab, &c->sf_comp, &c->sf_sorted, &c->sf_list, &c->mo_tab, &c->mo_rows, &c->rf_tab, &c->rf_rows, &c->gr_tab, &c->gr_comp,
+            &c->gr_sorted, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
             &c->ws_buf, &c->status, &c->hmap_keys, &c->hmap_par};
 }
 

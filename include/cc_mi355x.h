@@ -448,6 +448,27 @@ int cc_region_features(cc_ctx* ctx, const uint64_t* labels_dev, const void* valu
                        uint64_t* n_unique, uint64_t* ids_host, uint64_t* counts_host, double* sums_host,
                        float* mins_host, float* maxs_host, int64_t cap);
 
+/* --- region adjacency graph --------------------------------------------------------
+ * GraphWorkflow (graph/graph_workflow.py:9-74; initial_sub_graphs.py:115-129,
+ * merge_sub_graphs.py:128-138) over the whole volume in one read pass: labels_dev holds
+ * shape[0] x shape[1] x shape[2] (z, y, x) uint64 device elements.
+ *   nodes: the sorted distinct ids;
+ *   edges: the pairs (u, v), u < v, of ids carried by two voxels adjacent along z, y or x
+ *          (6-neighbourhood), sorted by (u, v), unique, as rows of two uint64;
+ *   sizes: per edge the number of such voxel faces.
+ * ignore_label != 0: a face with a 0 on either side makes no edge and 0 is no node.
+ * owned <= shape (from the origin): labels_dev is a piece of a larger volume with a read-only
+ * halo beyond the owned box; a face counts when its lower-coordinate voxel lies in the owned box,
+ * an id is a node when it occurs there.  owned == shape: the whole volume.
+ * Counts are always returned; nodes_host (nullable, node_cap entries) and edges_host / sizes_host
+ * (nullable together, edge_cap rows / entries) are written only when both caps suffice (call
+ * again with larger ones otherwise).  Ids must be below 2^32 - 1: status CC_ERR_ID_RANGE otherwise
+ * (relabel with cc_relabel_consecutive, which keeps the order, and call again).  Id 2^64-1 is
+ * reserved (error).  Every dimension must be below 2^31. */
+int cc_region_graph(cc_ctx* ctx, const uint64_t* labels_dev, const int64_t shape[3], const int64_t owned[3],
+                    int ignore_label, uint64_t* n_nodes, uint64_t* nodes_host, int64_t node_cap,
+                    uint64_t* n_edges, uint64_t* edges_host /* (n, 2) */, uint64_t* sizes_host, int64_t edge_cap);
+
 /* Seeded watershed per block (watershed/watershed_from_seeds.py:143-273, the WatershedFromSeeds
  * task of ThresholdAndWatershedWorkflow, thresholded_components_workflow.py:107-144): the seeds
  * (uint64 ids < 2^32 - 1, 0 = none; e.g. the thresholded components) grow over the input
