@@ -31,11 +31,11 @@ EXPORTS = (
     'cc_shard_dev_seam_pairs', 'cc_shard_dev_finish', 'cc_normalize_channels', 'cc_shard_dev_ok',
     'cc_comm_unique_id', 'cc_comm_create', 'cc_comm_destroy', 'cc_label_volume_sharded', 'cc_comm_info',
     'cc_label_sizes', 'cc_size_filter', 'cc_morphology', 'cc_region_features',
-    'cc_region_graph',
+    'cc_region_graph', 'cc_edge_features',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
-CC_ERR_ID_RANGE = -3          # cc_evaluate, cc_region_graph: ids beyond the key packing (include/cc_mi355x.h)
+CC_ERR_ID_RANGE = -3          # cc_evaluate, cc_region_graph, cc_edge_features: ids beyond the key packing (include/cc_mi355x.h)
 # CC_DTYPE_* of include/cc_mi355x.h (cc_channel_mean)
 DTYPES = {'float32': 0, 'float64': 1, 'uint8': 2, 'int8': 3, 'uint16': 4, 'int16': 5, 'uint32': 6,
           'int32': 7, 'uint64': 8, 'int64': 9}
@@ -161,6 +161,7 @@ def load(host_only=False):
         'cc_morphology': (I, [P, P, P, P, P, P, i64]),
         'cc_region_features': (I, [P, P, P, I, i64, P, P, P, P, P, P, i64]),
         'cc_region_graph': (I, [P, P, P, P, I, P, P, i64, P, P, P, i64]),
+        'cc_edge_features': (I, [P, P, P, I, P, P, I, P, P, P, P, P, P, P, P, P, i64]),
         'cc_channel_mean': (I, [P, P, I, P, P, i64, P]),
         'cc_gaussian_smooth_blocks': (I, [P, P, P, P, ctypes.c_double, P]),
         'cc_gaussian_taps': (I, [ctypes.c_double, P, I]),
@@ -347,6 +348,24 @@ def _region_features_float(raw, uint8_input):
     return table
 
 
+def _merge_min_max(inv, n, minimum, maximum):
+    """float32 minima / maxima of n groups, entry i belonging to group inv[i]: np.minimum /
+    np.maximum propagate a NaN; among equal zeros -0 is the minimum, +0 the maximum"""
+    mn, mx = np.full(n, np.inf, dtype=np.float32), np.full(n, -np.inf, dtype=np.float32)
+    with np.errstate(invalid='ignore'):
+        np.minimum.at(mn, inv, minimum)
+        np.maximum.at(mx, inv, maximum)
+    neg0 = (minimum == 0) & np.signbit(minimum)
+    hit = np.zeros(n, dtype=bool)
+    hit[inv[neg0]] = True
+    mn[hit & (mn == 0)] = np.float32(-0.0)
+    pos0 = (maximum == 0) & ~np.signbit(maximum)
+    hit = np.zeros(n, dtype=bool)
+    hit[inv[pos0]] = True
+    mx[hit & (mx == 0)] = np.float32(0.0)
+    return mn, mx
+
+
 def merge_region_features(raw_tables):
     """The raw tables (Context.region_features(raw=True)) of disjoint pieces of one volume merged
     into the raw table of the whole: per id the counts and the sums add (float64, in the order of
@@ -357,21 +376,11 @@ def merge_region_features(raw_tables):
     ids, inv = np.unique(cat['ids'], return_inverse=True)
     inv = inv.reshape(-1)
     out = {'ids': ids, 'count': np.zeros(len(ids), dtype=np.uint64), 'sum': np.zeros(len(ids), dtype=np.float64),
-           'minimum': np.full(len(ids), np.inf, dtype=np.float32), 'maximum': np.full(len(ids), -np.inf, dtype=np.float32)}
+           'minimum': None, 'maximum': None}
     np.add.at(out['count'], inv, cat['count'])
-    # np.minimum / np.maximum propagate a NaN; among equal zeros -0 is the minimum, +0 the maximum
     with np.errstate(invalid='ignore'):
         np.add.at(out['sum'], inv, cat['sum'])
-        np.minimum.at(out['minimum'], inv, cat['minimum'])
-        np.maximum.at(out['maximum'], inv, cat['maximum'])
-    neg0 = (cat['minimum'] == 0) & np.signbit(cat['minimum'])
-    hit = np.zeros(len(ids), dtype=bool)
-    hit[inv[neg0]] = True
-    out['minimum'][hit & (out['minimum'] == 0)] = np.float32(-0.0)
-    pos0 = (cat['maximum'] == 0) & ~np.signbit(cat['maximum'])
-    hit = np.zeros(len(ids), dtype=bool)
-    hit[inv[pos0]] = True
-    out['maximum'][hit & (out['maximum'] == 0)] = np.float32(0.0)
+    out['minimum'], out['maximum'] = _merge_min_max(inv, len(ids), cat['minimum'], cat['maximum'])
     return out
 
 
@@ -438,6 +447,114 @@ def merge_region_graphs(tables):
         first = np.flatnonzero(np.concatenate([[True], (edges[1:] != edges[:-1]).any(axis=1)]))
         edges, sizes = edges[first], np.add.reduceat(sizes, first)
     return {'nodes': nodes, 'edges': np.ascontiguousarray(edges), 'sizes': sizes.astype(np.uint64)}
+
+
+# the columns of an edge feature table (block_edge_features.py:146-148: n_feats = 10); a raw table
+# (Context.edge_features(raw=True)) is a dict of `edges`, the per-edge arrays RAW_EDGE_FEATURES,
+# `hist` (m, 256) uint32 and the flag `uint8_input`
+EDGE_FEATURES = ('mean', 'variance', 'min', 'q10', 'q25', 'q50', 'q75', 'q90', 'max', 'count')
+EDGE_QUANTILES = (10, 25, 50, 75, 90)
+EDGE_BINS = 256
+RAW_EDGE_FEATURES = (('count', np.uint64), ('sum', np.float64), ('sumsq', np.float64), ('minimum', np.float32),
+                     ('maximum', np.float32))
+
+
+def _raw_edge_features(raw):
+    out = {k: np.asarray(raw[k], dtype=t).reshape(-1) for k, t in RAW_EDGE_FEATURES}
+    out['edges'] = np.asarray(raw['edges'], dtype=np.uint64).reshape(-1, 2)
+    out['hist'] = np.asarray(raw['hist'], dtype=np.uint32).reshape(-1, EDGE_BINS)
+    out['uint8_input'] = bool(raw['uint8_input'])
+    assert all(len(out[k]) == len(out['edges']) for k in out if k != 'uint8_input')
+    return out
+
+
+def _edge_features_columns(raw, quantiles):
+    """(m, 10) float64 table EDGE_FEATURES from the per-edge arrays RAW_EDGE_FEATURES and the
+    (m, 5) quantiles: mean = sum / n, variance = max(0, sumsq / n - mean^2) (population); uint8
+    input: the sums are those of the integers, so mean, min and max are / 255 and the variance
+    / 255^2, once per edge."""
+    n = np.asarray(raw['count'], dtype=np.uint64).astype(np.float64)
+    table = np.zeros((len(n), len(EDGE_FEATURES)), dtype=np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean = np.asarray(raw['sum'], dtype=np.float64) / n
+        table[:, 0] = mean
+        table[:, 1] = np.maximum(np.asarray(raw['sumsq'], dtype=np.float64) / n - mean * mean, 0.)   # a NaN stays
+    table[:, 2] = np.asarray(raw['minimum'], dtype=np.float32).astype(np.float64)
+    table[:, 3:8] = quantiles
+    table[:, 8] = np.asarray(raw['maximum'], dtype=np.float32).astype(np.float64)
+    table[:, 9] = n
+    if raw['uint8_input']:
+        table[:, [0, 2, 8]] /= 255.
+        table[:, 1] /= 255. * 255.
+    return table
+
+
+def edge_quantiles(count, hist, uint8_input):
+    """The (m, 5) float64 quantiles EDGE_QUANTILES of m edges from their sample counts and (m, 256)
+    bins -- the host twin of the device's k_ef_quant, equal to it bit for bit.  For p:
+    k = max(1, ceil(p n / 100)), b = the first bin whose cumulative count reaches k; uint8 input:
+    b / 255 (the k-th smallest sample), float32: (b + (k - cum(b - 1) - 0.5) / h[b]) / 256 (inside
+    the bin of the k-th smallest sample).  NaN where the bins do not add up to the count (an edge
+    with a NaN sample, which is in no bin)."""
+    n = np.asarray(count, dtype=np.uint64).reshape(-1).astype(np.int64)
+    hist = np.asarray(hist, dtype=np.uint32).reshape(-1, EDGE_BINS).astype(np.int64)
+    out = np.full((len(n), len(EDGE_QUANTILES)), np.nan, dtype=np.float64)
+    cum = np.cumsum(hist, axis=1)
+    ok = np.flatnonzero((cum[:, -1] == n) & (n > 0)) if len(n) else np.zeros(0, dtype=np.int64)
+    n, hist, cum = n[ok], hist[ok], cum[ok]
+    rows = np.arange(len(ok))
+    for j, p in enumerate(EDGE_QUANTILES):
+        k = np.maximum(1, (p * n + 99) // 100)
+        b = (cum < k[:, None]).sum(axis=1)
+        below = cum[rows, b] - hist[rows, b]
+        if uint8_input:
+            out[ok, j] = b.astype(np.float64) / 255.
+        else:
+            out[ok, j] = (b.astype(np.float64) + ((k - below).astype(np.float64) - 0.5) / hist[rows, b].astype(np.float64)) / 256.
+    return out
+
+
+def edge_features_table(raw):
+    """The (m, 10) float64 edge feature table (columns EDGE_FEATURES, rows in the order of
+    raw['edges']) of a raw table, what MergeEdgeFeatures writes (merge_edge_features.py:65-70)."""
+    raw = _raw_edge_features(raw)
+    return _edge_features_columns(raw, edge_quantiles(raw['count'], raw['hist'], raw['uint8_input']))
+
+
+def merge_edge_features(raw_tables):
+    """The raw tables (Context.edge_features(raw=True)) of the pieces of one volume, each computed
+    on its piece plus the one-plane halo with `owned` (as merge_region_graphs' pieces), merged into
+    the raw table of the whole: per edge the counts, the bins and the sums add (float64, in the
+    order of the pieces: exact for uint8 and other inputs whose partial sums are representable),
+    the minima and maxima merge as in merge_region_features; sorted by (u, v).  The pieces must
+    agree in uint8_input; no piece gives an empty float32 table."""
+    tables = [_raw_edge_features(t) for t in raw_tables]
+    u8 = {t['uint8_input'] for t in tables}
+    assert len(u8) <= 1, 'the pieces must all come from uint8 or all from float32 values'
+    cat = {k: (np.concatenate([t[k] for t in tables]) if tables else np.zeros(0, dtype=d)) for k, d in RAW_EDGE_FEATURES}
+    edges = np.concatenate([t['edges'] for t in tables]) if tables else np.zeros((0, 2), dtype=np.uint64)
+    hist = np.concatenate([t['hist'] for t in tables]) if tables else np.zeros((0, EDGE_BINS), dtype=np.uint32)
+    m = 0
+    inv = np.zeros(0, dtype=np.int64)
+    first = inv
+    if len(edges):
+        order = np.lexsort((edges[:, 1], edges[:, 0]))
+        se = edges[order]
+        head = np.concatenate([[True], (se[1:] != se[:-1]).any(axis=1)])
+        first = order[head]
+        inv = np.empty(len(edges), dtype=np.int64)
+        inv[order] = np.cumsum(head) - 1
+        m = int(head.sum())
+    out = {'edges': np.ascontiguousarray(edges[first]).reshape(-1, 2), 'count': np.zeros(m, dtype=np.uint64),
+           'sum': np.zeros(m, dtype=np.float64), 'sumsq': np.zeros(m, dtype=np.float64),
+           'hist': np.zeros((m, EDGE_BINS), dtype=np.uint32), 'uint8_input': bool(u8.pop()) if u8 else False}
+    np.add.at(out['count'], inv, cat['count'])
+    np.add.at(out['hist'], inv, hist)
+    with np.errstate(invalid='ignore'):
+        np.add.at(out['sum'], inv, cat['sum'])
+        np.add.at(out['sumsq'], inv, cat['sumsq'])
+    out['minimum'], out['maximum'] = _merge_min_max(inv, m, cat['minimum'], cat['maximum'])
+    return out
 
 
 def comm_unique_id():
@@ -936,6 +1053,78 @@ class Context:
         for k in ('nodes', 'edges'):                   # back from the relabelled id space
             graph[k] = table[(graph[k] - first).astype(np.int64), 0]
         return graph
+
+    def edge_features(self, labels, values, ignore_label=True, owned=None, cap_hint=1 << 20, raw=False):
+        """EdgeFeaturesWorkflow for boundary maps (features/features_workflow.py:12-64) over the
+        whole volume on device: per edge of region_graph(labels, ignore_label, owned) the
+        statistics of `values` (a contiguous float32 or uint8 CUDA tensor of labels' shape; uint8 v
+        means v / 255) over the voxel faces where the two ids meet.  A face gives one sample, the
+        larger of its two voxels' values (for a face across the owned border the halo voxel's value
+        takes part), so an edge's sample count is its size in the graph.  Two passes over the
+        labels, one over the values.
+
+        Returns {'edges': (m, 2) uint64, 'features': (m, 10) float64} with the columns
+        EDGE_FEATURES: mean, variance (population), min, the quantiles 10 / 25 / 50 / 75 / 90, max,
+        count.  The quantiles come from 256 bins per edge (edge_quantiles): exact for uint8, less
+        than 1 / 256 from the sample quantile for float32 in [0, 1]; float32 values beyond [0, 1]
+        count in the end bins (mean, variance, min and max use the true value).  An edge with a
+        NaN sample has NaN features (but its count); no other edge is affected.
+        raw=True: the device state as a dict of numpy arrays -- edges, count (u64), sum, sumsq
+        (f64; uint8: of the integers, exact), minimum, maximum (f32; uint8: 0 .. 255), hist
+        ((m, 256) u32) and the flag uint8_input -- what merge_edge_features merges and
+        edge_features_table turns into the table.  cap_hint: the expected number of edges (a larger
+        count costs a second call).  Ids >= 2^32 - 1: as region_graph (relabelled on the device,
+        edges mapped back).  Affinity offsets, filter responses and 4-D values are not built."""
+        import torch
+        self._check_labels(labels)
+        assert labels.dim() == 3, 'labels must be 3-D (z, y, x)'
+        assert hasattr(values, 'data_ptr') and values.is_cuda and values.is_contiguous(), \
+            'values must be a contiguous CUDA tensor'
+        assert values.dtype in (torch.float32, torch.uint8), 'values must be float32 or uint8'
+        assert tuple(values.shape) == tuple(labels.shape), 'labels and values must have the same shape'
+        assert values.device == labels.device
+        shape = _i64(labels.shape)
+        own = shape if owned is None else _i64(owned)
+        assert own.shape == (3,) and (own >= 0).all() and (own <= shape).all(), 'owned must lie within labels.shape'
+        u8 = values.dtype == torch.uint8
+        L = load()
+
+        def call(lab):
+            ne = np.zeros(1, dtype=np.uint64)
+            cap = max(1, int(cap_hint))
+            while True:
+                out = {k: np.empty(cap, dtype=t) for k, t in RAW_EDGE_FEATURES}
+                edges, quant = np.empty((cap, 2), dtype=np.uint64), np.empty((cap, len(EDGE_QUANTILES)), dtype=np.float64)
+                hist = np.empty((cap, EDGE_BINS), dtype=np.uint32) if raw else None
+                rc = L.cc_edge_features(self._h, _ptr(lab), _ptr(values), 1 if u8 else 0, _ptr(shape), _ptr(own),
+                                        int(bool(ignore_label)), _ptr(ne), _ptr(edges), _ptr(out['count']),
+                                        _ptr(out['sum']), _ptr(out['sumsq']), _ptr(out['minimum']), _ptr(out['maximum']),
+                                        _ptr(quant), _ptr(hist) if raw else None, cap)
+                if rc != 0:
+                    return rc, None, None
+                if int(ne[0]) <= cap:
+                    break
+                cap = int(ne[0])
+            m = int(ne[0])
+            out = {k: v[:m].copy() for k, v in out.items()}
+            out['edges'] = edges[:m].copy()
+            out['uint8_input'] = u8
+            if raw:
+                out['hist'] = hist[:m].copy()
+            return 0, out, quant[:m]
+
+        rc, out, quant = call(labels)
+        if rc != 0:
+            if rc != CC_ERR_ID_RANGE:                  # CC_ERR_ID_RANGE: relabel and call again
+                _check(rc)
+            relabelled, table = self.relabel_consecutive(labels)
+            rc, out, quant = call(relabelled)
+            _check(rc)
+            first = table[0, 1] if len(table) else np.uint64(0)
+            out['edges'] = table[(out['edges'] - first).astype(np.int64), 0]   # monotone: the order stays
+        if raw:
+            return out
+        return {'edges': out['edges'], 'features': _edge_features_columns(out, quant)}
 
     def size_filter(self, labels, size_threshold=None, target_number=None, discard_ids=None, relabel=True,
                     out=None, cap_hint=1 << 20):

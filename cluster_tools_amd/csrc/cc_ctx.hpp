@@ -259,6 +259,7 @@ struct cc_ctx {
         mo_tab, mo_rows,                                  // morphology table and its sorted rows (cc_morphology.hip)
         rf_tab, rf_rows,                                  // region features table and its sorted entries (cc_region_features.hip)
         gr_tab, gr_comp, gr_sorted,                       // region graph: table, compacted and sorted entries (cc_graph.hip)
+        ef_tab,                                           // edge features: the dense per-edge state (cc_edge_features.hip)
         gs1, gs2, gs_tab,                                 // Gaussian prefilter temporaries (cc_prefilter.hip)
         mask_xmap,                                        // resized masks (cc_mask.hip)
         mlive,                                            // masked runs: blocks holding a mask voxel (k_mask_live)
@@ -309,7 +310,7 @@ static inline std::vector<DevBuf*> ctx_bufs(cc_ctx* c) {
             &c->scalars2, &c->flags, &c->map_ids, &c->map_ids2, &c->map_vals, &c->map_par, &c->big, &c->pairsl, &c->pc,
             &c->ipairs, &c->ipc, &c->iovf, &c->spec, &c->mark, &c->bflag, &c->ev_main, &c->ev_z, &c->ev_seg, &c->ev_gt,
             &c->ev_flag, &c->ev_part, &c->rl_wg, &c->sf_tab, &c->sf_comp, &c->sf_sorted, &c->sf_list, &c->mo_tab, &c->mo_rows, &c->rf_tab, &c->rf_rows, &c->gr_tab, &c->gr_comp,
-            &c->gr_sorted, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
+            &c->gr_sorted, &c->ef_tab, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
             &c->ws_buf, &c->status, &c->hmap_keys, &c->hmap_par};
 }
 

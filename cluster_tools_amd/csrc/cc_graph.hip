@@ -205,39 +205,46 @@ __global__ __launch_bounds__(256) void k_gr_unpack(const u64* __restrict__ ekey,
 
 }  // namespace cc
 
-static int region_graph_impl(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], const int64_t owned[3],
-                             int ignore_label, uint64_t* n_nodes, uint64_t* nodes_host, int64_t node_cap,
-                             uint64_t* n_edges, uint64_t* edges_host, uint64_t* sizes_host, int64_t edge_cap) {
-    CC_REQUIRE(c && shape && owned && n_nodes && n_edges && node_cap >= 0 && edge_cap >= 0, "bad arguments");
-    CC_REQUIRE((edges_host == nullptr) == (sizes_host == nullptr), "edges_host and sizes_host go together");
-    HIP_OK(hipSetDevice(c->device));
-    hipStream_t s = cstream(c);
-    *n_nodes = 0;
-    *n_edges = 0;
-    for (int d = 0; d < 3; ++d) {
-        CC_REQUIRE(shape[d] >= 0 && shape[d] < (1LL << 31), "region graph: every dimension must be in [0, 2^31)");
-        CC_REQUIRE(owned[d] >= 0 && owned[d] <= shape[d], "region graph: owned must lie within shape");
-    }
-    if (owned[0] == 0 || owned[1] == 0 || owned[2] == 0) return 0;
-    CC_REQUIRE(labels && ((uintptr_t)labels & 7) == 0, "labels must be an 8-byte aligned device pointer");
-    const unsigned __int128 nv = (unsigned __int128)((u64)shape[0] * (u64)shape[1]) * (u64)shape[2];
-    CC_REQUIRE(nv < ((unsigned __int128)1 << 60), "region graph: volume too large");
+// geometry of the tile walk over the owned box, rows = the rows of a wave's tile
+static cc::GrGeom gr_geom(const int64_t shape[3], const int64_t owned[3], int rows) {
     GrGeom g;
     g.Z = shape[0]; g.Y = shape[1]; g.X = shape[2];
     g.oz = owned[0]; g.oy = owned[1]; g.ox = owned[2];
     g.ntx = (g.ox + 63) / 64;
-    g.ntiles = g.ntx * ((g.oy + GR_R - 1) / GR_R);
+    g.ntiles = g.ntx * ((g.oy + rows - 1) / rows);
     g.wpc = (g.ntiles + GR_WAVES - 1) / GR_WAVES;
     // z chunks: long ones (each re-reads one plane) as long as ~4096 workgroups remain
     const int64_t chunks_want = std::max<int64_t>(1, 4096 / g.wpc);
     g.zc = std::min<int64_t>(128, std::max<int64_t>(16, g.oz / chunks_want));
     const int64_t nzc = (g.oz + g.zc - 1) / g.zc;
     CC_REQUIRE(g.wpc * nzc < (1LL << 31), "region graph: too many tiles");
-    const unsigned grid = (unsigned)(g.wpc * nzc);
+    return g;
+}
+static unsigned gr_grid(const cc::GrGeom& g) { return (unsigned)(g.wpc * ((g.oz + g.zc - 1) / g.zc)); }
+
+// The pass over the volume: afterwards c->gr_tab holds the table (keys | counts, `cap` slots each)
+// and c->gr_comp its compacted entries (nodes | edge keys | edge counts, `cap` slots each, nn nodes
+// and ne edges of them filled, unsorted).  hint: the expected number of entries.  False (and no
+// pass) when the owned box is empty.
+struct GrPass {
+    int64_t cap = 0, nn = 0, ne = 0;
+};
+static bool gr_pass(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], const int64_t owned[3], int ignore_label,
+                    int64_t hint, GrPass& p) {
+    hipStream_t s = cstream(c);
+    for (int d = 0; d < 3; ++d) {
+        CC_REQUIRE(shape[d] >= 0 && shape[d] < (1LL << 31), "region graph: every dimension must be in [0, 2^31)");
+        CC_REQUIRE(owned[d] >= 0 && owned[d] <= shape[d], "region graph: owned must lie within shape");
+    }
+    if (owned[0] == 0 || owned[1] == 0 || owned[2] == 0) return false;
+    CC_REQUIRE(labels && ((uintptr_t)labels & 7) == 0, "labels must be an 8-byte aligned device pointer");
+    const unsigned __int128 nv = (unsigned __int128)((u64)shape[0] * (u64)shape[1]) * (u64)shape[2];
+    CC_REQUIRE(nv < ((unsigned __int128)1 << 60), "region graph: volume too large");
+    const GrGeom g = gr_geom(shape, owned, GR_R);
+    const unsigned grid = gr_grid(g);
     c->counter.ensure(3 * sizeof(u32));
     int64_t cap = std::max<int64_t>(c->gr_cap, 1 << 16);
     {
-        const int64_t hint = (nodes_host ? node_cap : 0) + (edges_host ? edge_cap : 0);
         const int64_t want = 2 * std::min<int64_t>(std::min<int64_t>(hint, 4 * (int64_t)nv), 1LL << 27);
         while (cap < want) cap *= 2;
     }
@@ -267,29 +274,46 @@ static int region_graph_impl(cc_ctx* c, const uint64_t* labels, const int64_t sh
             continue;
         }
         c->gr_cap = cap;
-        *n_nodes = (uint64_t)nn;
-        *n_edges = (uint64_t)ne;
-        if ((nodes_host && node_cap < nn) || (edges_host && edge_cap < ne)) return 0;
-        if (!nodes_host && !edges_host) return 0;
-        // sorted nodes | sorted edge keys | sizes | rows (u, v)
-        c->gr_sorted.ensure((size_t)(nn + 4 * ne + 4) * sizeof(u64));
-        u64* nodes = c->gr_sorted.as<u64>();
-        u64* ekey = nodes + nn + 1;
-        u64* ecnt = ekey + ne + 1;
-        u64* uv = ecnt + ne + 1;
-        if (nodes_host && nn) {
-            launch(c, "radix_sort", [&] { prims::sort_keys<u64>(comp, nodes, nn, 0, 32, c->cub_tmp, s); });
-            HIP_OK(hipMemcpyAsync(nodes_host, nodes, nn * sizeof(u64), hipMemcpyDeviceToHost, s));
-        }
-        if (edges_host && ne) {
-            launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp + cap, ekey, comp + 2 * cap, ecnt, ne, 0, 64, c->cub_tmp, s); });
-            launch(c, "k_gr_unpack", [&] { k_gr_unpack<<<grid1d(ne), 256, 0, s>>>(ekey, ne, uv); });
-            HIP_OK(hipMemcpyAsync(edges_host, uv, 2 * ne * sizeof(u64), hipMemcpyDeviceToHost, s));
-            HIP_OK(hipMemcpyAsync(sizes_host, ecnt, ne * sizeof(u64), hipMemcpyDeviceToHost, s));
-        }
-        sync(c);
-        return 0;
+        p.cap = cap; p.nn = nn; p.ne = ne;
+        return true;
     }
+}
+
+static int region_graph_impl(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], const int64_t owned[3],
+                             int ignore_label, uint64_t* n_nodes, uint64_t* nodes_host, int64_t node_cap,
+                             uint64_t* n_edges, uint64_t* edges_host, uint64_t* sizes_host, int64_t edge_cap) {
+    CC_REQUIRE(c && shape && owned && n_nodes && n_edges && node_cap >= 0 && edge_cap >= 0, "bad arguments");
+    CC_REQUIRE((edges_host == nullptr) == (sizes_host == nullptr), "edges_host and sizes_host go together");
+    HIP_OK(hipSetDevice(c->device));
+    hipStream_t s = cstream(c);
+    *n_nodes = 0;
+    *n_edges = 0;
+    GrPass p;
+    if (!gr_pass(c, labels, shape, owned, ignore_label, (nodes_host ? node_cap : 0) + (edges_host ? edge_cap : 0), p)) return 0;
+    const int64_t cap = p.cap, nn = p.nn, ne = p.ne;
+    u64* comp = c->gr_comp.as<u64>();
+    *n_nodes = (uint64_t)nn;
+    *n_edges = (uint64_t)ne;
+    if ((nodes_host && node_cap < nn) || (edges_host && edge_cap < ne)) return 0;
+    if (!nodes_host && !edges_host) return 0;
+    // sorted nodes | sorted edge keys | sizes | rows (u, v)
+    c->gr_sorted.ensure((size_t)(nn + 4 * ne + 4) * sizeof(u64));
+    u64* nodes = c->gr_sorted.as<u64>();
+    u64* ekey = nodes + nn + 1;
+    u64* ecnt = ekey + ne + 1;
+    u64* uv = ecnt + ne + 1;
+    if (nodes_host && nn) {
+        launch(c, "radix_sort", [&] { prims::sort_keys<u64>(comp, nodes, nn, 0, 32, c->cub_tmp, s); });
+        HIP_OK(hipMemcpyAsync(nodes_host, nodes, nn * sizeof(u64), hipMemcpyDeviceToHost, s));
+    }
+    if (edges_host && ne) {
+        launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp + cap, ekey, comp + 2 * cap, ecnt, ne, 0, 64, c->cub_tmp, s); });
+        launch(c, "k_gr_unpack", [&] { k_gr_unpack<<<grid1d(ne), 256, 0, s>>>(ekey, ne, uv); });
+        HIP_OK(hipMemcpyAsync(edges_host, uv, 2 * ne * sizeof(u64), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(sizes_host, ecnt, ne * sizeof(u64), hipMemcpyDeviceToHost, s));
+    }
+    sync(c);
+    return 0;
 }
 
 extern "C" {

@@ -1,1 +1,1 @@
-from .features_workflow import RegionFeaturesWorkflow  # noqa: F401
+from .features_workflow import EdgeFeaturesWorkflow, RegionFeaturesWorkflow  # noqa: F401

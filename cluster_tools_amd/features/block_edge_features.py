@@ -1,0 +1,124 @@
+#! /usr/bin/python
+"""BlockEdgeFeatures task + job (reference: cluster_tools/features/block_edge_features.py).
+
+Same task surface as the reference (block_edge_features.py:21-94): parameters input_path /
+input_key / labels_path / labels_key / graph_path / output_path / dependency, the task config's
+keys offsets, filters, sigmas, halo, apply_in_2d and channel_agglomeration, the log target
+<tmp>/block_edge_features.log, shape (and ignore_label) read from graph_path:s0/sub_graphs, and one
+"processed block" line per listed block.  Only the boundary-map features are built
+(_accumulate_block's extractBlockFeaturesFromBoundaryMaps branch, :146-148): a non-None offsets
+(affinity features) or filters (filter responses), or a 4-D input, raises.  sigmas, halo,
+apply_in_2d and channel_agglomeration only concern those and are ignored.
+The job's compute runs on the MI355X through cc_edge_features; one GPU job covers the whole
+volume.  Input: uint8 stays uint8 (v means v / 255, the reference's normalize, applied once per
+edge when the table is made), anything else goes through astype('float32').  The result, the raw
+table of Context.edge_features(raw=True), goes to <tmp>/edge_features.npz, which MergeEdgeFeatures
+reads.  The reference's per-block varlen dataset output_path:s0/sub_features is not created: its
+only reader is the reference's own merge job.  The costs and multicut stages are not built.
+"""
+import json
+import os
+
+import numpy as np
+
+from cluster_tools_amd.luigi_compat import Task, Parameter, TaskParameter
+from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
+from cluster_tools_amd.graph.initial_sub_graphs import SUB_GRAPH_KEY
+import cluster_tools_amd.utils.volume_utils as vu
+import cluster_tools_amd.utils.function_utils as fu
+
+NOT_BUILT = ('%s is set in the block_edge_features task config: edge features from %s are not built '
+             '(boundary maps only: 3-D input, offsets = None, filters = None)')
+
+
+def raw_table_path(tmp_folder):
+    return os.path.join(tmp_folder, 'edge_features.npz')
+
+
+class BlockEdgeFeaturesBase(Task):
+    task_name = 'block_edge_features'
+    src_file = os.path.abspath(__file__)
+
+    input_path = Parameter()
+    input_key = Parameter()
+    labels_path = Parameter()
+    labels_key = Parameter()
+    graph_path = Parameter()
+    output_path = Parameter()
+    dependency = TaskParameter(default=DummyTask())
+
+    def requires(self):
+        return self.dependency
+
+    @staticmethod
+    def default_task_config():
+        config = LocalTask.default_task_config()
+        config.update({'offsets': None, 'filters': None, 'sigmas': None, 'halo': [0, 0, 0],
+                       'apply_in_2d': False, 'channel_agglomeration': 'mean'})
+        return config
+
+    def run_impl(self):
+        shebang, block_shape, roi_begin, roi_end = self.global_config_values()
+        self.init(shebang)
+        config = self.get_task_config()
+        if config.get('offsets') is not None:
+            raise RuntimeError(NOT_BUILT % ('offsets', 'affinities'))
+        if config.get('filters') is not None:
+            raise RuntimeError(NOT_BUILT % ('filters', 'filter responses'))
+        with vu.file_reader(self.graph_path, 'r') as f:
+            g = f[SUB_GRAPH_KEY]
+            shape, ignore_label = tuple(g.attrs['shape']), bool(g.attrs['ignore_label'])
+        in_shape = tuple(vu.get_shape(self.input_path, self.input_key))
+        if len(in_shape) == 4:
+            raise RuntimeError('%s:%s is 4-D: edge features from affinities and filter responses are not built '
+                               '(boundary maps only)' % (self.input_path, self.input_key))
+        assert in_shape == shape, 'input %s and the graph\'s volume %s differ in shape' % (in_shape, shape)
+        config.update({'input_path': self.input_path, 'input_key': self.input_key,
+                       'labels_path': self.labels_path, 'labels_key': self.labels_key,
+                       'output_path': self.output_path, 'block_shape': list(block_shape),
+                       'graph_path': self.graph_path, 'ignore_label': ignore_label, 'tmp_folder': self.tmp_folder})
+        block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end)
+        n_jobs = 1                     # one GPU job covers the volume
+        self.prepare_jobs(n_jobs, block_list, config)
+        self.submit_jobs(n_jobs)
+        self.wait_for_jobs()
+        self.check_jobs(n_jobs)
+
+
+class BlockEdgeFeaturesLocal(BlockEdgeFeaturesBase, LocalTask):
+    pass
+
+
+def block_edge_features(job_id, config_path):
+    import torch
+    from cluster_tools_amd import _lib
+    fu.log('start processing job %i' % job_id)
+    fu.log('reading config from %s' % config_path)
+    with open(config_path) as f:
+        config = json.load(f)
+    with vu.file_reader(config['labels_path'], 'r') as f:
+        labels = np.ascontiguousarray(f[config['labels_key']][:].astype(np.uint64, copy=False))
+    with vu.file_reader(config['input_path'], 'r') as f:
+        input_ = f[config['input_key']][:]
+    if input_.dtype != np.dtype('uint8'):
+        input_ = input_.astype('float32')
+    input_ = np.ascontiguousarray(input_)
+    assert input_.shape == labels.shape, 'input %s and labels %s differ in shape' % (input_.shape, labels.shape)
+    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
+        dev = torch.from_numpy(labels.view(np.int64)).to(ctx.torch_device())
+        vals = torch.from_numpy(input_).to(ctx.torch_device())
+        raw = ctx.edge_features(dev, vals, ignore_label=bool(config['ignore_label']), raw=True)
+    for b in config['block_list']:
+        fu.log_block_success(b)
+    save_path = raw_table_path(config['tmp_folder'])
+    fu.log('saving results to %s' % save_path)
+    np.savez(save_path, **raw)
+    fu.log_job_success(job_id)
+
+
+if __name__ == '__main__':
+    import sys
+    path = sys.argv[1]
+    assert os.path.exists(path), path
+    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
+    block_edge_features(job_id, path)

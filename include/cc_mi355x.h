@@ -469,6 +469,34 @@ int cc_region_graph(cc_ctx* ctx, const uint64_t* labels_dev, const int64_t shape
                     int ignore_label, uint64_t* n_nodes, uint64_t* nodes_host, int64_t node_cap,
                     uint64_t* n_edges, uint64_t* edges_host /* (n, 2) */, uint64_t* sizes_host, int64_t edge_cap);
 
+/* --- edge features of the region adjacency graph -------------------------------------
+ * EdgeFeaturesWorkflow for boundary maps (features/features_workflow.py:12-64,
+ * block_edge_features.py:146-148, merge_edge_features.py:65-70) over the whole volume: labels_dev,
+ * shape, owned and ignore_label as for cc_region_graph, values_dev the same number of values of
+ * value_type (CC_RF_FLOAT32, 4-byte aligned, or CC_RF_UINT8).  The edges are cc_region_graph's;
+ * every voxel face of an edge gives one sample, the larger of its two voxels' values (a NaN
+ * counts as the largest; for a face across the owned border the halo voxel's value takes part).
+ * Per edge, in the order of the edges:
+ *   counts  the samples (cc_region_graph's sizes);
+ *   sums, sumsq  the float64 sums of the samples and of their squares (uint8: of the integers,
+ *          exact);
+ *   mins, maxs  the smallest and the largest sample (uint8: 0 .. 255);
+ *   quant  five float64 per edge, the quantiles 10, 25, 50, 75, 90 from a 256-bin histogram: uint8 v
+ *          in bin v, a float32 v in bin min(255, floor(clamp(v, 0, 1) * 256)); with
+ *          k = max(1, ceil(p n / 100)) and b the first bin whose cumulative count reaches k the
+ *          quantile is b / 255 (uint8) or (b + (k - cum(b - 1) - 0.5) / h[b]) / 256 (float32);
+ *   hist   (nullable) the 256 bins (uint32).
+ * An edge with a NaN sample has NaN sums, minimum, maximum and quantiles (the NaN is in no bin);
+ * no other edge is affected.  n_edges is always returned; the host arrays (edge_cap entries /
+ * rows each) are written only when edge_cap >= n_edges (call again with larger ones otherwise).
+ * Errors: CC_ERR_ID_RANGE and the reserved id as cc_region_graph; an edge of 2^32 or more faces;
+ * 1 KiB of device memory per edge that is not free.  Neither input is modified. */
+int cc_edge_features(cc_ctx* ctx, const uint64_t* labels_dev, const void* values_dev, int value_type,
+                     const int64_t shape[3], const int64_t owned[3], int ignore_label, uint64_t* n_edges,
+                     uint64_t* edges_host /* (n, 2) */, uint64_t* counts_host, double* sums_host, double* sumsq_host,
+                     float* mins_host, float* maxs_host, double* quant_host /* (n, 5) */,
+                     uint32_t* hist_host /* (n, 256), nullable */, int64_t edge_cap);
+
 /* Seeded watershed per block (watershed/watershed_from_seeds.py:143-273, the WatershedFromSeeds
  * task of ThresholdAndWatershedWorkflow, thresholded_components_workflow.py:107-144): the seeds
  * (uint64 ids < 2^32 - 1, 0 = none; e.g. the thresholded components) grow over the input
