@@ -31,11 +31,11 @@ EXPORTS = (
     'cc_shard_dev_seam_pairs', 'cc_shard_dev_finish', 'cc_normalize_channels', 'cc_shard_dev_ok',
     'cc_comm_unique_id', 'cc_comm_create', 'cc_comm_destroy', 'cc_label_volume_sharded', 'cc_comm_info',
     'cc_label_sizes', 'cc_size_filter', 'cc_morphology', 'cc_region_features',
-    'cc_region_graph', 'cc_edge_features',
+    'cc_region_graph', 'cc_edge_features', 'cc_label_overlaps', 'cc_max_overlaps',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
-CC_ERR_ID_RANGE = -3          # cc_evaluate, cc_region_graph, cc_edge_features: ids beyond the key packing (include/cc_mi355x.h)
+CC_ERR_ID_RANGE = -3          # cc_evaluate, cc_region_graph, cc_edge_features, cc_label_overlaps: ids beyond the key packing (include/cc_mi355x.h)
 # CC_DTYPE_* of include/cc_mi355x.h (cc_channel_mean)
 DTYPES = {'float32': 0, 'float64': 1, 'uint8': 2, 'int8': 3, 'uint16': 4, 'int16': 5, 'uint32': 6,
           'int32': 7, 'uint64': 8, 'int64': 9}
@@ -162,6 +162,8 @@ def load(host_only=False):
         'cc_region_features': (I, [P, P, P, I, i64, P, P, P, P, P, P, i64]),
         'cc_region_graph': (I, [P, P, P, P, I, P, P, i64, P, P, P, i64]),
         'cc_edge_features': (I, [P, P, P, I, P, P, I, P, P, P, P, P, P, P, P, P, i64]),
+        'cc_label_overlaps': (I, [P, P, P, I, P, P, I, u64, P, P, P, P, i64]),
+        'cc_max_overlaps': (I, [P, P, P, P, i64, u64, P, P]),
         'cc_channel_mean': (I, [P, P, I, P, P, i64, P]),
         'cc_gaussian_smooth_blocks': (I, [P, P, P, P, ctypes.c_double, P]),
         'cc_gaussian_taps': (I, [ctypes.c_double, P, I]),
@@ -447,6 +449,67 @@ def merge_region_graphs(tables):
         first = np.flatnonzero(np.concatenate([[True], (edges[1:] != edges[:-1]).any(axis=1)]))
         edges, sizes = edges[first], np.add.reduceat(sizes, first)
     return {'nodes': nodes, 'edges': np.ascontiguousarray(edges), 'sizes': sizes.astype(np.uint64)}
+
+
+# a table of label overlaps (Context.label_overlaps): the triples (ws id, label id, voxels) as a
+# dict of the 1-D uint64 arrays ws_ids, label_ids and counts, sorted by (ws id, label id)
+LABEL_OVERLAPS = ('ws_ids', 'label_ids', 'counts')
+
+
+def _label_overlaps(table):
+    out = {k: np.asarray(table[k], dtype=np.uint64).reshape(-1) for k in LABEL_OVERLAPS}
+    assert len(out['ws_ids']) == len(out['label_ids']) == len(out['counts'])
+    return out
+
+
+def merge_label_overlaps(tables):
+    """The overlaps (Context.label_overlaps) of the pieces of one volume -- disjoint boxes cut on
+    block boundaries, so that every block of the block grid lies in one piece -- merged into the
+    overlaps of the whole: the counts of equal (ws id, label id) added (what MergeNodeLabels does
+    with the blocks' overlaps, merge_node_labels.py:145-155), sorted by (ws id, label id)."""
+    tables = [_label_overlaps(t) for t in tables]
+    if not tables:
+        return {k: np.zeros(0, dtype=np.uint64) for k in LABEL_OVERLAPS}
+    ws, lab, cnt = (np.concatenate([t[k] for t in tables]) for k in LABEL_OVERLAPS)
+    if len(ws):
+        order = np.lexsort((lab, ws))
+        ws, lab, cnt = ws[order], lab[order], cnt[order]
+        first = np.flatnonzero(np.concatenate([[True], (ws[1:] != ws[:-1]) | (lab[1:] != lab[:-1])]))
+        ws, lab, cnt = ws[first], lab[first], np.add.reduceat(cnt, first)
+    return {'ws_ids': ws, 'label_ids': lab, 'counts': cnt.astype(np.uint64)}
+
+
+def max_overlaps_table(overlaps, number_of_labels, with_counts=False):
+    """cc_max_overlaps in numpy: per node in [0, number_of_labels) the label of its largest
+    overlap, the smallest label when several attain it (a definition of this project: nifty walks
+    an unordered map); a node without overlap gets label 0 and count 0, triples with ws id >=
+    number_of_labels or count 0 are ignored.  (n,) uint64, or (n, 2) [label, count] with
+    with_counts."""
+    t = _label_overlaps(overlaps)
+    n = int(number_of_labels)
+    keep = (t['ws_ids'] < np.uint64(n)) & (t['counts'] != 0)
+    ws, lab, cnt = (t[k][keep] for k in LABEL_OVERLAPS)
+    out = np.zeros((n, 2), dtype=np.uint64)
+    if len(ws):
+        order = np.lexsort((lab, ~cnt, ws))              # by node, the largest count first, then the smallest label
+        ws, lab, cnt = ws[order], lab[order], cnt[order]
+        first = np.flatnonzero(np.concatenate([[True], ws[1:] != ws[:-1]]))
+        out[ws[first].astype(np.int64), 0] = lab[first]
+        out[ws[first].astype(np.int64), 1] = cnt[first]
+    return out if with_counts else np.ascontiguousarray(out[:, 0])
+
+
+def overlaps_csr(overlaps, number_of_labels):
+    """All overlaps per node as a CSR: a dict of uint64 arrays offsets (n + 1,), labels and counts;
+    node i overlaps labels[offsets[i]:offsets[i + 1]] (ascending) with counts[...] voxels.  Triples
+    with ws id >= number_of_labels are dropped."""
+    t = merge_label_overlaps([overlaps])                 # sorted by (ws id, label id)
+    n = int(number_of_labels)
+    keep = t['ws_ids'] < np.uint64(n)
+    ws, lab, cnt = (t[k][keep] for k in LABEL_OVERLAPS)
+    per_node = np.bincount(ws.astype(np.int64), minlength=n) if n else np.zeros(0, dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum(per_node)]).astype(np.uint64)
+    return {'offsets': offsets, 'labels': np.ascontiguousarray(lab), 'counts': np.ascontiguousarray(cnt)}
 
 
 # the columns of an edge feature table (block_edge_features.py:146-148: n_feats = 10); a raw table
@@ -883,6 +946,124 @@ class Context:
                 arr[:] = table[(arr - table[0, 1]).astype(np.int64), 0]
         o = np.lexsort((b, a))
         return a[o], b[o], c[o]
+
+    def _label_overlaps(self, ws, labels, block_shape, ignore_label, cap_hint):
+        """label_overlaps, and whether the triples cc_label_overlaps left on the device are in the
+        caller's id spaces (no volume had to be relabelled)"""
+        import torch
+        self._check_labels(ws)
+        assert ws.dim() == 3, 'ws must be 3-D (z, y, x)'
+        assert hasattr(labels, 'data_ptr') and labels.is_cuda and labels.is_contiguous(), \
+            'labels must be a contiguous CUDA tensor'
+        assert labels.shape == ws.shape and labels.device == ws.device, 'ws and labels must have one shape and device'
+        elem = labels.element_size()
+        assert (elem in (1, 2, 4, 8) and not labels.dtype.is_floating_point and not labels.dtype.is_complex
+                and labels.dtype != torch.bool), 'labels must be of an integer dtype of 1, 2, 4 or 8 bytes'
+        shape = _i64(ws.shape)
+        bs = shape if block_shape is None else _i64(block_shape)
+        assert bs.shape == (3,) and (bs >= 1).all()
+        use_ignore = ignore_label is not None
+        L = load()
+
+        def call(w, lab, ignore):
+            nn = np.zeros(1, dtype=np.uint64)
+            cap = max(1, int(cap_hint))
+            while True:
+                out = {k: np.empty(cap, dtype=np.uint64) for k in LABEL_OVERLAPS}
+                rc = L.cc_label_overlaps(self._h, _ptr(w), _ptr(lab), lab.element_size(), _ptr(shape), _ptr(bs),
+                                         int(use_ignore), int(ignore) if use_ignore else 0, _ptr(nn),
+                                         _ptr(out['ws_ids']), _ptr(out['label_ids']), _ptr(out['counts']), cap)
+                if rc != 0:
+                    return rc, None
+                if int(nn[0]) <= cap:
+                    break
+                cap = int(nn[0])
+            return 0, {k: v[:int(nn[0])].copy() for k, v in out.items()}
+
+        rc, table = call(ws, labels, ignore_label)
+        if rc == 0:
+            return table, True
+        if rc != CC_ERR_ID_RANGE:                      # CC_ERR_ID_RANGE: relabel and call again
+            _check(rc)
+
+        def too_large(a, limit):
+            v = a.view(torch.int64)
+            return bool((v < 0).any()) or bool((v >= limit).any())
+        maps = {}
+        if too_large(ws, 2 ** 31):
+            ws, maps['ws_ids'] = self.relabel_consecutive(ws)
+        if elem == 4:                                  # only 2^32 - 1 is beyond the packing: widened, then as uint64
+            wide = labels.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        elif elem == 8:
+            wide = labels
+        else:
+            wide = None
+        if wide is not None and too_large(wide, 2 ** 32 - 1):
+            labels, table = self.relabel_consecutive(wide)
+            maps['label_ids'] = table
+            if use_ignore:       # the ignore label in the new id space (an unused id if absent)
+                k = np.searchsorted(table[:, 0], np.uint64(ignore_label))
+                present = k < len(table) and table[k, 0] == np.uint64(ignore_label)
+                ignore_label = int(table[k, 1]) if present else int(table[-1, 1]) + 1
+        torch.cuda.current_stream(ws.device).synchronize()
+        rc, table = call(ws, labels, ignore_label)
+        _check(rc)
+        for k, m in maps.items():                      # back from the relabelled id spaces (monotone: still sorted)
+            if len(table[k]):
+                table[k] = m[(table[k] - m[0, 1]).astype(np.int64), 0]
+        return table, False
+
+    def label_overlaps(self, ws, labels, block_shape=None, ignore_label=None, cap_hint=1 << 20):
+        """The overlaps of NodeLabelWorkflow (node_labels/block_node_labels.py:133-165 over the
+        block grid, summed as merge_node_labels.py:145-155 does) over the whole volume on device, in
+        one read pass: how many voxels every id of the contiguous 3-D uint64 (torch int64 / uint64)
+        CUDA tensor `ws` shares with every id of `labels`, a contiguous CUDA tensor of the same
+        shape and of any integer dtype of 1, 2, 4 or 8 bytes, its bits read as unsigned (8 +
+        element size bytes are read per voxel).  Returns a dict of the uint64 numpy arrays ws_ids,
+        label_ids and counts, sorted by (ws id, label id).  block_shape: the block grid (None: one
+        block, the whole volume); a block whose ws is all 0 contributes nothing.  ignore_label:
+        voxels with this label are not counted (None: every voxel counts, label 0 included).
+        cap_hint: the expected number of triples (a larger count costs a second call).
+
+        The device table packs (ws id, label id) into one 64-bit key (ws < 2^31, label < 2^32 -
+        1).  A volume with larger ids is first relabelled consecutively on the device
+        (relabel_consecutive: order-preserving, 0 stays 0; the id 2^64 - 1 is reserved there) and
+        the ids are mapped back."""
+        return self._label_overlaps(ws, labels, block_shape, ignore_label, cap_hint)[0]
+
+    def max_overlaps(self, number_of_labels, overlaps=None, with_counts=False):
+        """cc_max_overlaps: per node in [0, number_of_labels) the label of its largest overlap
+        (ties: the smallest label; no overlap: label 0, count 0), on the device.  overlaps: a table
+        of triples (e.g. merge_label_overlaps of several pieces), uploaded; None: the triples the
+        last label_overlaps of this context left on the device (in the id spaces of the device
+        call: use node_labels unless no volume had ids beyond the key packing).  Returns the
+        (number_of_labels,) uint64 labels, or (number_of_labels, 2) [label, count] with
+        with_counts."""
+        import torch
+        n_labels = int(number_of_labels)
+        out_l, out_c = np.zeros(n_labels, dtype=np.uint64), np.zeros(n_labels, dtype=np.uint64)
+        if overlaps is None:
+            dev, n = [None] * 3, -1
+        else:
+            t = _label_overlaps(overlaps)
+            n = len(t['ws_ids'])
+            dev = [torch.from_numpy(np.ascontiguousarray(t[k]).view(np.int64)).to(self.torch_device())
+                   for k in LABEL_OVERLAPS]
+            torch.cuda.current_stream(dev[0].device).synchronize()
+        _check(load().cc_max_overlaps(self._h, _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]), n, n_labels, _ptr(out_l),
+                                      _ptr(out_c)))
+        return np.stack([out_l, out_c], axis=1) if with_counts else out_l
+
+    def node_labels(self, ws, labels, number_of_labels, block_shape=None, ignore_label=None, with_counts=False,
+                    cap_hint=1 << 20):
+        """NodeLabelWorkflow with max_overlap=True on device: label_overlaps(ws, labels,
+        block_shape, ignore_label), then per node in [0, number_of_labels) the label it shares the
+        most voxels with -- the smallest such label when several share as many, 0 for a node
+        without overlap.  Returns the (number_of_labels,) uint64 vector, or (number_of_labels, 2)
+        as [label, count] with with_counts.  The triples stay on the device between the two steps
+        unless a volume had to be relabelled for the key packing."""
+        table, on_device = self._label_overlaps(ws, labels, block_shape, ignore_label, cap_hint)
+        return self.max_overlaps(number_of_labels, None if on_device else table, with_counts)
 
     def relabel_consecutive(self, labels, out=None, cap_hint=1 << 20):
         """RelabelWorkflow (relabel_workflow.py:10-60, find_labeling.py:84-120) on device:

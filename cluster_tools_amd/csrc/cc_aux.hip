@@ -1,5 +1,5 @@
 // cc_aux.hip -- second translation unit of libcc_mi355x.so: segmentation evaluation
-// (cc_eval.hip), consecutive relabelling (cc_relabel.hip), the size filter
+// (cc_eval.hip), node labels (cc_node_labels.hip), consecutive relabelling (cc_relabel.hip), the size filter
 // (cc_size_filter.hip), the morphology table (cc_morphology.hip), the region features
 // (cc_region_features.hip), the region adjacency graph (cc_graph.hip), its edge features
 // (cc_edge_features.hip), the channel / Gaussian prefilter (cc_prefilter.hip) and the seeded
@@ -27,6 +27,7 @@ __global__ __launch_bounds__(NTHREADS) void k_block_stats(Geom g, const float* _
 }  // namespace cc
 
 #include "cc_eval.hip"
+#include "cc_node_labels.hip"
 #include "cc_relabel.hip"
 #include "cc_size_filter.hip"
 #include "cc_morphology.hip"

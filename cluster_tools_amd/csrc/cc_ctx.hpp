@@ -260,6 +260,7 @@ struct cc_ctx {
         rf_tab, rf_rows,                                  // region features table and its sorted entries (cc_region_features.hip)
         gr_tab, gr_comp, gr_sorted,                       // region graph: table, compacted and sorted entries (cc_graph.hip)
         ef_tab,                                           // edge features: the dense per-edge state (cc_edge_features.hip)
+        nl_tab, nl_flag, nl_comp, nl_sorted, nl_max,      // node labels: tables, block flags, compacted and sorted triples, argmax (cc_node_labels.hip)
         gs1, gs2, gs_tab,                                 // Gaussian prefilter temporaries (cc_prefilter.hip)
         mask_xmap,                                        // resized masks (cc_mask.hip)
         mlive,                                            // masked runs: blocks holding a mask voxel (k_mask_live)
@@ -271,6 +272,8 @@ struct cc_ctx {
     int64_t mo_cap = 0;      // table slots of the last cc_morphology
     int64_t rf_cap = 0;      // table slots of the last cc_region_features
     int64_t gr_cap = 0;      // table slots of the last cc_region_graph
+    int64_t nl_cap = 0;      // table slots of the last cc_label_overlaps
+    int64_t nl_n = -1;       // triples the last cc_label_overlaps left in nl_sorted (-1: none)
     // last run
     int64_t n_blocks = 0;
     uint64_t n_labels = 0;
@@ -310,7 +313,7 @@ static inline std::vector<DevBuf*> ctx_bufs(cc_ctx* c) {
             &c->scalars2, &c->flags, &c->map_ids, &c->map_ids2, &c->map_vals, &c->map_par, &c->big, &c->pairsl, &c->pc,
             &c->ipairs, &c->ipc, &c->iovf, &c->spec, &c->mark, &c->bflag, &c->ev_main, &c->ev_z, &c->ev_seg, &c->ev_gt,
             &c->ev_flag, &c->ev_part, &c->rl_wg, &c->sf_tab, &c->sf_comp, &c->sf_sorted, &c->sf_list, &c->mo_tab, &c->mo_rows, &c->rf_tab, &c->rf_rows, &c->gr_tab, &c->gr_comp,
-            &c->gr_sorted, &c->ef_tab, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
+            &c->gr_sorted, &c->ef_tab, &c->nl_tab, &c->nl_flag, &c->nl_comp, &c->nl_sorted, &c->nl_max, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
             &c->ws_buf, &c->status, &c->hmap_keys, &c->hmap_par};
 }
 

@@ -357,6 +357,38 @@ int cc_evaluate(cc_ctx* ctx, const uint64_t* seg_dev, const uint64_t* gt_dev, co
 /* contingency table of the last cc_evaluate (unordered); returns its size (copies min(size, cap)) */
 int64_t cc_get_overlaps(cc_ctx* ctx, uint64_t* seg_ids, uint64_t* gt_ids, uint64_t* counts, int64_t cap);
 
+/* --- node labels: overlaps of two label volumes -----------------------------------
+ * NodeLabelWorkflow (node_labels/node_label_workflow.py; block_node_labels.py:133-165,
+ * merge_node_labels.py:145-155) over the whole volume in one read pass: ws_dev holds
+ * shape[0] x shape[1] x shape[2] (z, y, x) uint64 device elements (8-byte aligned), labels_dev as
+ * many unsigned elements of label_elem_size = 1, 2, 4 or 8 bytes (aligned to their size; read in
+ * whole aligned 16-byte words, each of which holds at least one element of the volume), widened to
+ * uint64.  Over the block grid block_shape a block whose ws sums to 0 contributes nothing (this
+ * only ever concerns the overlaps of ws id 0); use_ignore != 0: voxels whose label equals
+ * ignore_label are not counted; use_ignore == 0: every voxel counts, label 0 included.
+ * The result is the triples (ws id, label id, voxels), sorted by (ws id, label id), compacted on
+ * the device.  *n is always returned; the three host arrays (nullable together, cap entries each)
+ * are written only when cap >= *n (call again with cap >= *n otherwise); cap also sizes the device
+ * table.  The triples stay on the device, in the context, for cc_max_overlaps.
+ * Key packing: ws ids < 2^31, label ids < 2^32 - 1, fewer than 2^31 blocks, every dimension below
+ * 2^31; an id beyond it gives status CC_ERR_ID_RANGE (relabel with cc_relabel_consecutive, which
+ * keeps the order and keeps 0, and call again; it reserves the id 2^64 - 1).  Neither input is
+ * modified. */
+int cc_label_overlaps(cc_ctx* ctx, const uint64_t* ws_dev, const void* labels_dev, int label_elem_size,
+                      const int64_t shape[3], const int64_t block_shape[3], int use_ignore, uint64_t ignore_label,
+                      uint64_t* n, uint64_t* ws_ids_host, uint64_t* label_ids_host, uint64_t* counts_host,
+                      int64_t cap);
+/* The label of the largest overlap for every node in [0, number_of_labels), from n triples in
+ * device memory (any order, any 64-bit ids and counts, 8-byte aligned); n < 0 (and the three
+ * arrays NULL): the triples the last cc_label_overlaps on this ctx left.
+ * out_labels_host[i] = the label with the largest count among the triples of ws id i, the
+ * smallest such label when several attain it; out_counts_host[i] (nullable) = that count.  A node
+ * without a triple gets label 0 and count 0; triples with ws id >= number_of_labels or count 0
+ * are ignored.  The result does not depend on the order of the triples.
+ * number_of_labels < 2^32 - 256. */
+int cc_max_overlaps(cc_ctx* ctx, const uint64_t* ws_ids_dev, const uint64_t* label_ids_dev, const uint64_t* counts_dev,
+                    int64_t n, uint64_t number_of_labels, uint64_t* out_labels_host, uint64_t* out_counts_host);
+
 /* --- consecutive relabelling --------------------------------------------------
  * RelabelWorkflow (relabel/relabel_workflow.py:10-60; find_labeling.py:84-120): the sorted unique
  * ids of labels_dev get new ids start, start + 1, ... (start = 0 when id 0 occurs, else 1); the
