@@ -31,7 +31,7 @@ EXPORTS = (
     'cc_shard_dev_seam_pairs', 'cc_shard_dev_finish', 'cc_normalize_channels', 'cc_shard_dev_ok',
     'cc_comm_unique_id', 'cc_comm_create', 'cc_comm_destroy', 'cc_label_volume_sharded', 'cc_comm_info',
     'cc_label_sizes', 'cc_size_filter', 'cc_morphology', 'cc_region_features',
-    'cc_region_graph', 'cc_edge_features', 'cc_label_overlaps', 'cc_max_overlaps',
+    'cc_region_graph', 'cc_edge_features', 'cc_label_overlaps', 'cc_max_overlaps', 'cc_affinity_features',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -162,6 +162,7 @@ def load(host_only=False):
         'cc_region_features': (I, [P, P, P, I, i64, P, P, P, P, P, P, i64]),
         'cc_region_graph': (I, [P, P, P, P, I, P, P, i64, P, P, P, i64]),
         'cc_edge_features': (I, [P, P, P, I, P, P, I, P, P, P, P, P, P, P, P, P, i64]),
+        'cc_affinity_features': (I, [P, P, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, i64]),
         'cc_label_overlaps': (I, [P, P, P, I, P, P, I, u64, P, P, P, P, i64]),
         'cc_max_overlaps': (I, [P, P, P, P, i64, u64, P, P]),
         'cc_channel_mean': (I, [P, P, I, P, P, i64, P]),
@@ -514,7 +515,9 @@ def overlaps_csr(overlaps, number_of_labels):
 
 # the columns of an edge feature table (block_edge_features.py:146-148: n_feats = 10); a raw table
 # (Context.edge_features(raw=True)) is a dict of `edges`, the per-edge arrays RAW_EDGE_FEATURES,
-# `hist` (m, 256) uint32 and the flag `uint8_input`
+# `hist` (m, 256) uint32 and the flag `uint8_input`; a raw table of affinity features
+# (Context.affinity_features(raw=True)) carries `offsets` (n, 3) int64 as well: its counts are sample
+# counts, and an edge may have none (count 0, sums 0, empty bins, minimum +inf, maximum -inf)
 EDGE_FEATURES = ('mean', 'variance', 'min', 'q10', 'q25', 'q50', 'q75', 'q90', 'max', 'count')
 EDGE_QUANTILES = (10, 25, 50, 75, 90)
 EDGE_BINS = 256
@@ -528,6 +531,8 @@ def _raw_edge_features(raw):
     out['hist'] = np.asarray(raw['hist'], dtype=np.uint32).reshape(-1, EDGE_BINS)
     out['uint8_input'] = bool(raw['uint8_input'])
     assert all(len(out[k]) == len(out['edges']) for k in out if k != 'uint8_input')
+    if 'offsets' in raw:
+        out['offsets'] = np.asarray(raw['offsets'], dtype=np.int64).reshape(-1, 3)
     return out
 
 
@@ -535,7 +540,8 @@ def _edge_features_columns(raw, quantiles):
     """(m, 10) float64 table EDGE_FEATURES from the per-edge arrays RAW_EDGE_FEATURES and the
     (m, 5) quantiles: mean = sum / n, variance = max(0, sumsq / n - mean^2) (population); uint8
     input: the sums are those of the integers, so mean, min and max are / 255 and the variance
-    / 255^2, once per edge."""
+    / 255^2, once per edge.  A table with `offsets` (affinity features): an edge without a sample
+    has a row of ten zeros."""
     n = np.asarray(raw['count'], dtype=np.uint64).astype(np.float64)
     table = np.zeros((len(n), len(EDGE_FEATURES)), dtype=np.float64)
     with np.errstate(invalid='ignore', divide='ignore'):
@@ -549,20 +555,25 @@ def _edge_features_columns(raw, quantiles):
     if raw['uint8_input']:
         table[:, [0, 2, 8]] /= 255.
         table[:, 1] /= 255. * 255.
+    if 'offsets' in raw:
+        table[n == 0] = 0.
     return table
 
 
-def edge_quantiles(count, hist, uint8_input):
+def edge_quantiles(count, hist, uint8_input, zero_count=False):
     """The (m, 5) float64 quantiles EDGE_QUANTILES of m edges from their sample counts and (m, 256)
     bins -- the host twin of the device's k_ef_quant, equal to it bit for bit.  For p:
     k = max(1, ceil(p n / 100)), b = the first bin whose cumulative count reaches k; uint8 input:
     b / 255 (the k-th smallest sample), float32: (b + (k - cum(b - 1) - 0.5) / h[b]) / 256 (inside
     the bin of the k-th smallest sample).  NaN where the bins do not add up to the count (an edge
-    with a NaN sample, which is in no bin)."""
+    with a NaN sample, which is in no bin).  zero_count (tables with `offsets`): an edge without a
+    sample has zeros, as the device leaves them."""
     n = np.asarray(count, dtype=np.uint64).reshape(-1).astype(np.int64)
     hist = np.asarray(hist, dtype=np.uint32).reshape(-1, EDGE_BINS).astype(np.int64)
     out = np.full((len(n), len(EDGE_QUANTILES)), np.nan, dtype=np.float64)
     cum = np.cumsum(hist, axis=1)
+    if zero_count and len(n):
+        out[(n == 0) & (cum[:, -1] == 0)] = 0.
     ok = np.flatnonzero((cum[:, -1] == n) & (n > 0)) if len(n) else np.zeros(0, dtype=np.int64)
     n, hist, cum = n[ok], hist[ok], cum[ok]
     rows = np.arange(len(ok))
@@ -581,7 +592,7 @@ def edge_features_table(raw):
     """The (m, 10) float64 edge feature table (columns EDGE_FEATURES, rows in the order of
     raw['edges']) of a raw table, what MergeEdgeFeatures writes (merge_edge_features.py:65-70)."""
     raw = _raw_edge_features(raw)
-    return _edge_features_columns(raw, edge_quantiles(raw['count'], raw['hist'], raw['uint8_input']))
+    return _edge_features_columns(raw, edge_quantiles(raw['count'], raw['hist'], raw['uint8_input'], 'offsets' in raw))
 
 
 def merge_edge_features(raw_tables):
@@ -590,10 +601,16 @@ def merge_edge_features(raw_tables):
     the raw table of the whole: per edge the counts, the bins and the sums add (float64, in the
     order of the pieces: exact for uint8 and other inputs whose partial sums are representable),
     the minima and maxima merge as in merge_region_features; sorted by (u, v).  The pieces must
-    agree in uint8_input; no piece gives an empty float32 table."""
+    agree in uint8_input; no piece gives an empty float32 table.
+    Affinity tables (with `offsets`; Context.affinity_features(raw=True)) merge too: the tables of
+    one volume and graph computed from disjoint subsets of the channels.  Minima and maxima merge
+    with +inf / -inf, an edge without a sample's, as identities, and the offsets are concatenated in
+    the order of the tables.  Tables with and without `offsets` do not mix."""
     tables = [_raw_edge_features(t) for t in raw_tables]
     u8 = {t['uint8_input'] for t in tables}
     assert len(u8) <= 1, 'the pieces must all come from uint8 or all from float32 values'
+    assert len({'offsets' in t for t in tables}) <= 1, \
+        'tables with offsets (affinity features) and without (boundary features) cannot be merged'
     cat = {k: (np.concatenate([t[k] for t in tables]) if tables else np.zeros(0, dtype=d)) for k, d in RAW_EDGE_FEATURES}
     edges = np.concatenate([t['edges'] for t in tables]) if tables else np.zeros((0, 2), dtype=np.uint64)
     hist = np.concatenate([t['hist'] for t in tables]) if tables else np.zeros((0, EDGE_BINS), dtype=np.uint32)
@@ -617,6 +634,8 @@ def merge_edge_features(raw_tables):
         np.add.at(out['sum'], inv, cat['sum'])
         np.add.at(out['sumsq'], inv, cat['sumsq'])
     out['minimum'], out['maximum'] = _merge_min_max(inv, m, cat['minimum'], cat['maximum'])
+    if tables and 'offsets' in tables[0]:
+        out['offsets'] = np.concatenate([t['offsets'] for t in tables])
     return out
 
 
@@ -1255,7 +1274,8 @@ class Context:
         ((m, 256) u32) and the flag uint8_input -- what merge_edge_features merges and
         edge_features_table turns into the table.  cap_hint: the expected number of edges (a larger
         count costs a second call).  Ids >= 2^32 - 1: as region_graph (relabelled on the device,
-        edges mapped back).  Affinity offsets, filter responses and 4-D values are not built."""
+        edges mapped back).  Affinity maps with offsets: affinity_features.  Filter responses are
+        not built."""
         import torch
         self._check_labels(labels)
         assert labels.dim() == 3, 'labels must be 3-D (z, y, x)'
@@ -1290,6 +1310,82 @@ class Context:
             out = {k: v[:m].copy() for k, v in out.items()}
             out['edges'] = edges[:m].copy()
             out['uint8_input'] = u8
+            if raw:
+                out['hist'] = hist[:m].copy()
+            return 0, out, quant[:m]
+
+        rc, out, quant = call(labels)
+        if rc != 0:
+            if rc != CC_ERR_ID_RANGE:                  # CC_ERR_ID_RANGE: relabel and call again
+                _check(rc)
+            relabelled, table = self.relabel_consecutive(labels)
+            rc, out, quant = call(relabelled)
+            _check(rc)
+            first = table[0, 1] if len(table) else np.uint64(0)
+            out['edges'] = table[(out['edges'] - first).astype(np.int64), 0]   # monotone: the order stays
+        if raw:
+            return out
+        return {'edges': out['edges'], 'features': _edge_features_columns(out, quant)}
+
+    def affinity_features(self, labels, affinities, offsets, ignore_label=True, cap_hint=1 << 20, raw=False):
+        """EdgeFeaturesWorkflow with `offsets` (block_edge_features.py:135-145) over the whole
+        volume on device: per edge of region_graph(labels, ignore_label) the statistics of the
+        affinities over the pairs of voxels that the offsets connect across it.  `affinities`: a
+        contiguous (C, Z, Y, X) float32 or uint8 CUDA tensor (uint8 v means v / 255); `offsets`: n
+        integer triples (dz, dy, dx), 1 <= n <= 64, n <= C, none (0, 0, 0), any sign, diagonal and
+        long-range; channel c < n belongs to offsets[c], channels >= n are never read.  For every
+        c < n and every voxel p whose partner q = p + offsets[c] lies in the volume, the pair gives
+        the edge (min, max) of labels[p], labels[q] one sample, affinities[c, p] -- unless the two
+        ids are equal, one of them is 0 under ignore_label, or the pair is no edge of the graph
+        (two segments that do not touch: skipped, no error).
+
+        Returns what edge_features returns, with two differences: count is the number of samples
+        (with the three unit offsets, in any order and sign, the edge's size in the graph), and an
+        edge may have no sample: its row is ten zeros; in a raw table its count, sums and bins are
+        0, its minimum +inf and its maximum -inf.  A raw table also carries `offsets`, (n, 3)
+        int64.  cap_hint and ids >= 2^32 - 1: as edge_features.  Pieces with `owned` are not
+        offered: a long-range pair's edge may exist only in another piece's graph."""
+        import torch
+        self._check_labels(labels)
+        assert labels.dim() == 3, 'labels must be 3-D (z, y, x)'
+        assert hasattr(affinities, 'data_ptr') and affinities.is_cuda and affinities.is_contiguous(), \
+            'affinities must be a contiguous CUDA tensor'
+        assert affinities.dtype in (torch.float32, torch.uint8), 'affinities must be float32 or uint8'
+        assert affinities.dim() == 4 and tuple(affinities.shape[1:]) == tuple(labels.shape), \
+            'affinities must be 4-D (c, z, y, x) with the spatial shape of labels'
+        assert affinities.device == labels.device, 'labels and affinities must be on the same device'
+        offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+        assert offs.ndim == 2 and offs.shape[1] == 3 and np.array_equal(offs, np.asarray(offsets)), \
+            'offsets must be n integer triples (dz, dy, dx)'
+        assert 1 <= len(offs) <= 64, 'the number of offsets must be in [1, 64]'
+        assert len(offs) <= affinities.shape[0], \
+            '%i offsets need at least as many channels, affinities has %i' % (len(offs), affinities.shape[0])
+        assert offs.any(axis=1).all(), 'an offset (0, 0, 0) pairs every voxel with itself'
+        shape = _i64(labels.shape)
+        u8 = affinities.dtype == torch.uint8
+        L = load()
+
+        def call(lab):
+            ne = np.zeros(1, dtype=np.uint64)
+            cap = max(1, int(cap_hint))
+            while True:
+                out = {k: np.empty(cap, dtype=t) for k, t in RAW_EDGE_FEATURES}
+                edges, quant = np.empty((cap, 2), dtype=np.uint64), np.empty((cap, len(EDGE_QUANTILES)), dtype=np.float64)
+                hist = np.empty((cap, EDGE_BINS), dtype=np.uint32) if raw else None
+                rc = L.cc_affinity_features(self._h, _ptr(lab), _ptr(affinities), 1 if u8 else 0, _ptr(shape), len(offs),
+                                            _ptr(offs), int(bool(ignore_label)), _ptr(ne), _ptr(edges), _ptr(out['count']),
+                                            _ptr(out['sum']), _ptr(out['sumsq']), _ptr(out['minimum']),
+                                            _ptr(out['maximum']), _ptr(quant), _ptr(hist) if raw else None, cap)
+                if rc != 0:
+                    return rc, None, None
+                if int(ne[0]) <= cap:
+                    break
+                cap = int(ne[0])
+            m = int(ne[0])
+            out = {k: v[:m].copy() for k, v in out.items()}
+            out['edges'] = edges[:m].copy()
+            out['uint8_input'] = u8
+            out['offsets'] = offs.copy()
             if raw:
                 out['hist'] = hist[:m].copy()
             return 0, out, quant[:m]

@@ -2,7 +2,7 @@
 // (cc_eval.hip), node labels (cc_node_labels.hip), consecutive relabelling (cc_relabel.hip), the size filter
 // (cc_size_filter.hip), the morphology table (cc_morphology.hip), the region features
 // (cc_region_features.hip), the region adjacency graph (cc_graph.hip), its edge features
-// (cc_edge_features.hip), the channel / Gaussian prefilter (cc_prefilter.hip) and the seeded
+// (cc_edge_features.hip, from affinity maps cc_affinity_features.hip), the channel / Gaussian prefilter (cc_prefilter.hip) and the seeded
 // watershed (cc_watershed.hip), with their C-ABI entries.
 //
 // A unit of its own because the HIP runtime loads a code object whole, every kernel of it, at
@@ -34,5 +34,6 @@ __global__ __launch_bounds__(NTHREADS) void k_block_stats(Geom g, const float* _
 #include "cc_region_features.hip"
 #include "cc_graph.hip"
 #include "cc_edge_features.hip"
+#include "cc_affinity_features.hip"
 #include "cc_prefilter.hip"
 #include "cc_watershed.hip"

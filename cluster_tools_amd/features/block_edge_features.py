@@ -5,16 +5,21 @@ Same task surface as the reference (block_edge_features.py:21-94): parameters in
 input_key / labels_path / labels_key / graph_path / output_path / dependency, the task config's
 keys offsets, filters, sigmas, halo, apply_in_2d and channel_agglomeration, the log target
 <tmp>/block_edge_features.log, shape (and ignore_label) read from graph_path:s0/sub_graphs, and one
-"processed block" line per listed block.  Only the boundary-map features are built
-(_accumulate_block's extractBlockFeaturesFromBoundaryMaps branch, :146-148): a non-None offsets
-(affinity features) or filters (filter responses), or a 4-D input, raises.  sigmas, halo,
-apply_in_2d and channel_agglomeration only concern those and are ignored.
-The job's compute runs on the MI355X through cc_edge_features; one GPU job covers the whole
-volume.  Input: uint8 stays uint8 (v means v / 255, the reference's normalize, applied once per
-edge when the table is made), anything else goes through astype('float32').  The result, the raw
-table of Context.edge_features(raw=True), goes to <tmp>/edge_features.npz, which MergeEdgeFeatures
-reads.  The reference's per-block varlen dataset output_path:s0/sub_features is not created: its
-only reader is the reference's own merge job.  The costs and multicut stages are not built.
+"processed block" line per listed block.  Two of _accumulate_block's branches are built: the
+boundary-map features (extractBlockFeaturesFromBoundaryMaps, :146-148; 3-D input, offsets = None)
+through cc_edge_features, and the affinity features (extractBlockFeaturesFromAffinityMaps,
+:135-145; offsets set, a 4-D (C, Z, Y, X) input with C >= len(offsets) whose spatial shape is the
+graph's, of which only the first len(offsets) channels are read) through cc_affinity_features.
+offsets on a 3-D input raises, as the reference asserts, and so does a 4-D input without offsets
+or a non-None filters (filter responses).  sigmas, halo, apply_in_2d and channel_agglomeration only
+concern the filters and are ignored.
+The job's compute runs on the MI355X; one GPU job covers the whole volume.  Input: uint8 stays
+uint8 (v means v / 255, the reference's normalize, applied once per edge when the table is made),
+anything else goes through astype('float32').  The result, the raw table of
+Context.edge_features(raw=True) or Context.affinity_features(raw=True), goes to
+<tmp>/edge_features.npz, which MergeEdgeFeatures reads.  The reference's per-block varlen dataset
+output_path:s0/sub_features is not created: its only reader is the reference's own merge job.  The
+costs and multicut stages are not built.
 """
 import json
 import os
@@ -27,8 +32,7 @@ from cluster_tools_amd.graph.initial_sub_graphs import SUB_GRAPH_KEY
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
 
-NOT_BUILT = ('%s is set in the block_edge_features task config: edge features from %s are not built '
-             '(boundary maps only: 3-D input, offsets = None, filters = None)')
+NOT_BUILT = '%s is set in the block_edge_features task config: edge features from %s are not built%s'
 
 
 def raw_table_path(tmp_folder):
@@ -61,17 +65,24 @@ class BlockEdgeFeaturesBase(Task):
         shebang, block_shape, roi_begin, roi_end = self.global_config_values()
         self.init(shebang)
         config = self.get_task_config()
-        if config.get('offsets') is not None:
-            raise RuntimeError(NOT_BUILT % ('offsets', 'affinities'))
+        offsets = config.get('offsets')
         if config.get('filters') is not None:
-            raise RuntimeError(NOT_BUILT % ('filters', 'filter responses'))
+            raise RuntimeError(NOT_BUILT % ('filters', 'filter responses', ' (filters = None only)'))
         with vu.file_reader(self.graph_path, 'r') as f:
             g = f[SUB_GRAPH_KEY]
             shape, ignore_label = tuple(g.attrs['shape']), bool(g.attrs['ignore_label'])
         in_shape = tuple(vu.get_shape(self.input_path, self.input_key))
+        if offsets is not None and len(in_shape) != 4:
+            raise RuntimeError(NOT_BUILT % ('offsets', 'affinities', ' from a %i-D input: offsets need a (C, Z, Y, X) '
+                                            'input' % len(in_shape)))
         if len(in_shape) == 4:
-            raise RuntimeError('%s:%s is 4-D: edge features from affinities and filter responses are not built '
-                               '(boundary maps only)' % (self.input_path, self.input_key))
+            if offsets is None:
+                raise RuntimeError('%s:%s is 4-D and offsets is not set: edge features from filter responses are not '
+                                   'built (affinities need offsets)' % (self.input_path, self.input_key))
+            if in_shape[0] < len(offsets):
+                raise RuntimeError('%s:%s has %i channels, fewer than the %i offsets of the block_edge_features task '
+                                   'config' % (self.input_path, self.input_key, in_shape[0], len(offsets)))
+            in_shape = in_shape[1:]
         assert in_shape == shape, 'input %s and the graph\'s volume %s differ in shape' % (in_shape, shape)
         config.update({'input_path': self.input_path, 'input_key': self.input_key,
                        'labels_path': self.labels_path, 'labels_key': self.labels_key,
@@ -98,16 +109,22 @@ def block_edge_features(job_id, config_path):
         config = json.load(f)
     with vu.file_reader(config['labels_path'], 'r') as f:
         labels = np.ascontiguousarray(f[config['labels_key']][:].astype(np.uint64, copy=False))
+    offsets = config.get('offsets')
     with vu.file_reader(config['input_path'], 'r') as f:
-        input_ = f[config['input_key']][:]
+        ds = f[config['input_key']]
+        input_ = ds[:] if offsets is None else ds[:len(offsets)]       # only the offsets' channels are read
     if input_.dtype != np.dtype('uint8'):
         input_ = input_.astype('float32')
     input_ = np.ascontiguousarray(input_)
-    assert input_.shape == labels.shape, 'input %s and labels %s differ in shape' % (input_.shape, labels.shape)
+    assert input_.shape[input_.ndim - 3:] == labels.shape, \
+        'input %s and labels %s differ in shape' % (input_.shape, labels.shape)
     with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
         dev = torch.from_numpy(labels.view(np.int64)).to(ctx.torch_device())
         vals = torch.from_numpy(input_).to(ctx.torch_device())
-        raw = ctx.edge_features(dev, vals, ignore_label=bool(config['ignore_label']), raw=True)
+        if offsets is None:
+            raw = ctx.edge_features(dev, vals, ignore_label=bool(config['ignore_label']), raw=True)
+        else:
+            raw = ctx.affinity_features(dev, vals, offsets, ignore_label=bool(config['ignore_label']), raw=True)
     for b in config['block_list']:
         fu.log_block_success(b)
     save_path = raw_table_path(config['tmp_folder'])

@@ -3,10 +3,11 @@ cluster_tools/features/features_workflow.py).
 
 EdgeFeaturesWorkflow (features_workflow.py:12-64): the same parameters (max_jobs_merge included),
 the n5 / zarr check of the input and label paths, get_config and the task chain BlockEdgeFeatures
--> MergeEdgeFeatures, writing the float64 (n_edges, 10) table of per-edge boundary-map statistics
-(mean, variance, min, q10, q25, q50, q75, q90, max, count) for the edges of graph_path:graph_key,
-which GraphWorkflow must have written from the same labels.  Affinity offsets, filter responses,
-4-D input, the per-block s0/sub_features and the costs and multicut stages are not built.
+-> MergeEdgeFeatures, writing the float64 (n_edges, 10) table of per-edge statistics (mean,
+variance, min, q10, q25, q50, q75, q90, max, count) for the edges of graph_path:graph_key, which
+GraphWorkflow must have written from the same labels: of a 3-D boundary map, or, with `offsets` in
+the block_edge_features task config, of a 4-D (C, Z, Y, X) affinity map.  Filter responses, the
+per-block s0/sub_features and the costs and multicut stages are not built.
 
 RegionFeaturesWorkflow: the same
 parameters and task chain RegionFeatures -> MergeRegionFeatures, writing the (maxId + 1,

@@ -11,7 +11,9 @@ on its intermediate dataset).  A graph without edges gets a (0, 10) dataset that
 One host job (it never touches the GPU) loads the raw table BlockEdgeFeatures saved to
 <tmp>/edge_features.npz, verifies that its edges and sample counts are the graph's edges and
 edge_sizes -- a graph made with another ignore_label setting, or from other labels, fails here,
-naming both -- and writes the table (_lib.edge_features_table).
+naming both -- and writes the table (_lib.edge_features_table).  A raw table with `offsets`
+(affinity features) has sample counts that are not the graph's sizes: only its edges are checked,
+and the dataset gets the attribute offsets beside the two others.
 """
 import json
 import os
@@ -62,7 +64,7 @@ class MergeEdgeFeaturesLocal(MergeEdgeFeaturesBase, LocalTask):
     pass
 
 
-def write_table(f, key, table):
+def write_table(f, key, table, offsets=None):
     """the (n_edges, 10) float64 table as the reference lays it out; no chunk for no edges"""
     from cluster_tools_amd._lib import EDGE_FEATURES
     table = np.asarray(table, dtype=np.float64).reshape(-1, len(EDGE_FEATURES))
@@ -74,6 +76,8 @@ def write_table(f, key, table):
         ds = f.create_dataset(key, shape=table.shape, dtype='float64', chunks=chunks, compression='gzip')
     ds.attrs['n_features'] = len(EDGE_FEATURES)
     ds.attrs['feature_names'] = list(EDGE_FEATURES)
+    if offsets is not None:
+        ds.attrs['offsets'] = [[int(d) for d in o] for o in offsets]
 
 
 def merge_edge_features(job_id, config_path):
@@ -92,11 +96,11 @@ def merge_edge_features(job_id, config_path):
     if edges.shape != graph['edges'].shape or not np.array_equal(edges, graph['edges']):
         raise RuntimeError('the %i edges of %s are not the %i edges of the graph %s (another ignore_label '
                            'setting or other labels?)' % (len(edges), save_path, len(graph['edges']), where))
-    if not np.array_equal(counts, graph['sizes']):
+    if 'offsets' not in raw and not np.array_equal(counts, graph['sizes']):
         raise RuntimeError('the sample counts of %s are not the edge_sizes of the graph %s' % (save_path, where))
     table = edge_features_table(raw)
     with vu.file_reader(config['output_path']) as f:
-        write_table(f, config['output_key'], table)
+        write_table(f, config['output_key'], table, raw.get('offsets'))
     fu.log('wrote the features of %i edges to %s:%s' % (len(table), config['output_path'], config['output_key']))
     fu.log_job_success(job_id)
 

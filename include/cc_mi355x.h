@@ -529,6 +529,28 @@ int cc_edge_features(cc_ctx* ctx, const uint64_t* labels_dev, const void* values
                      float* mins_host, float* maxs_host, double* quant_host /* (n, 5) */,
                      uint32_t* hist_host /* (n, 256), nullable */, int64_t edge_cap);
 
+/* --- edge features of the region adjacency graph from affinity maps -------------------
+ * EdgeFeaturesWorkflow with `offsets` (block_edge_features.py:135-145) over the whole volume.
+ * labels_dev, shape and ignore_label as for cc_region_graph (owned = shape); affinities_dev holds at
+ * least n_offsets channels of shape[0] * shape[1] * shape[2] values of value_type each, channel c
+ * belonging to offsets[3 c .. 3 c + 2] = (dz, dy, dx) (a host array; any sign, diagonal and
+ * long-range; 1 <= n_offsets <= 64, no offset (0, 0, 0): errors with a message).  The edges are
+ * cc_region_graph's.  For every channel c and every voxel p whose partner q = p + offsets[c] lies
+ * in the volume, the pair gives the edge (min, max) of its two ids the sample affinities[c, p],
+ * unless the ids are equal, one of them is 0 under ignore_label, or the pair is no edge of the
+ * graph (segments that do not touch).  An offset as long as an extent gives no sample.
+ * counts are the samples per edge (with the three unit offsets: cc_region_graph's sizes); sums,
+ * sumsq, mins, maxs, quant and hist as for cc_edge_features.  An edge without a sample has count 0,
+ * sums 0, empty bins, quantiles 0, minimum +inf and maximum -inf.  n_edges, edge_cap and the
+ * errors as for cc_edge_features (CC_ERR_ID_RANGE included); an edge of 2^32 or more samples is an
+ * error.  Neither input is modified. */
+int cc_affinity_features(cc_ctx* ctx, const uint64_t* labels_dev, const void* affinities_dev, int value_type,
+                         const int64_t shape[3], int n_offsets, const int64_t* offsets /* host, 3 n */,
+                         int ignore_label, uint64_t* n_edges, uint64_t* edges_host /* (n, 2) */,
+                         uint64_t* counts_host, double* sums_host, double* sumsq_host, float* mins_host,
+                         float* maxs_host, double* quant_host /* (n, 5) */,
+                         uint32_t* hist_host /* (n, 256), nullable */, int64_t edge_cap);
+
 /* Seeded watershed per block (watershed/watershed_from_seeds.py:143-273, the WatershedFromSeeds
  * task of ThresholdAndWatershedWorkflow, thresholded_components_workflow.py:107-144): the seeds
  * (uint64 ids < 2^32 - 1, 0 = none; e.g. the thresholded components) grow over the input
