@@ -32,6 +32,7 @@ EXPORTS = (
     'cc_comm_unique_id', 'cc_comm_create', 'cc_comm_destroy', 'cc_label_volume_sharded', 'cc_comm_info',
     'cc_label_sizes', 'cc_size_filter', 'cc_morphology', 'cc_region_features',
     'cc_region_graph', 'cc_edge_features', 'cc_label_overlaps', 'cc_max_overlaps', 'cc_affinity_features',
+    'cc_distance_transform',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -172,6 +173,7 @@ def load(host_only=False):
         'cc_resize_mask_nearest': (I, [P, P, P, P, i64, i64, P]),
         'cc_watershed_from_seeds': (I, [P, P, P, P, P, P, P, P]),
         'cc_normalize_channels': (I, [P, P, i64, P, P, I, P]),
+        'cc_distance_transform': (I, [P, P, P, P, I, P, I, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -901,6 +903,32 @@ class Context:
         finally:
             _check(load().cc_set_option(self._h, 2, 0))
         return out, int(rounds[0])
+
+    def distance_transform(self, objects, block_shape=None, apply_2d=True, pixel_pitch=None, squared=False, out=None):
+        """_apply_dt's distance transform (watershed/watershed.py:140-161) on device, per block of
+        block_shape (None: the whole volume): `objects` is a uint8 CUDA tensor (Z, Y, X), non-zero
+        = object voxel (what threshold(..., mode='greater') writes); every voxel gets the Euclidean
+        distance to the nearest object voxel of its block (apply_2d: of its z-slice of the block),
+        0 on object voxels, as float32; pixel_pitch = (pz, py, px) scales the axes (3-D only);
+        squared=True (isotropic only) gives the exact squared distance as uint32 (returned as a
+        torch int32 tensor holding those bits when torch has no uint32).  See include/cc_mi355x.h
+        for the definition.  Defaults as the reference's task config (apply_dt_2d, pixel_pitch)."""
+        import torch
+        assert hasattr(objects, 'data_ptr') and objects.is_cuda and objects.dtype == torch.uint8
+        assert objects.dim() == 3 and objects.is_contiguous()
+        shape = _i64(objects.shape)
+        bs = _i64(objects.shape if block_shape is None else block_shape)
+        assert len(bs) == 3
+        pitch = None if pixel_pitch is None else np.ascontiguousarray(np.asarray(pixel_pitch, dtype=np.float64))
+        assert pitch is None or pitch.shape == (3,)
+        odt = getattr(torch, 'uint32', torch.int32) if squared else torch.float32
+        if out is None:
+            out = torch.empty(tuple(objects.shape), dtype=odt, device=objects.device)
+        assert out.is_cuda and out.element_size() == 4 and out.shape == objects.shape and out.is_contiguous()
+        assert out.dtype.is_floating_point != bool(squared)
+        _check(load().cc_distance_transform(self._h, _ptr(objects), _ptr(shape), _ptr(bs), int(bool(apply_2d)),
+                                            _ptr(pitch), int(bool(squared)), _ptr(out)))
+        return out
 
     def evaluate(self, seg, gt, block_shape, ignore_label=0):
         """EvaluationWorkflow (evaluation/evaluation_workflow.py:46-84) on device: overlaps per

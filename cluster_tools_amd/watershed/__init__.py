@@ -1,0 +1,1 @@
+from .distance_transform import DistanceTransformBase, DistanceTransformLocal  # noqa: F401

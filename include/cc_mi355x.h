@@ -574,6 +574,36 @@ int cc_watershed_from_seeds(cc_ctx* ctx, const float* in_dev, const uint64_t* se
 int cc_normalize_channels(cc_ctx* ctx, const float* in_dev, int64_t n_channels, const int64_t shape[3],
                           const int64_t block_shape[3], int agg, float* out_dev);
 
+/* --- Euclidean distance transform of object masks, per block ---------------------------
+ * The first stage of the reference's distance-transform watershed (_apply_dt,
+ * watershed/watershed.py:140-161: vigra.filters.distanceTransform of the thresholded block, per
+ * z-slice or in 3-D, optionally with a pixel_pitch).  objects_dev holds shape[0] x shape[1] x
+ * shape[2] (z, y, x) uint8 device elements; any non-zero voxel is an object voxel (what
+ * cc_threshold writes for `input > threshold`).
+ *   blocks  the volume is cut from the origin with block_shape, the last block per axis clipped;
+ *           blocks are independent (no voxel sees an object voxel of another block);
+ *           block_shape >= shape gives the whole-volume transform.
+ *   domain  apply_2d = 0: a whole block; apply_2d != 0: each z-slice of each block (z ignored).
+ *   pitch   (pz, py, px) doubles, NULL = (1, 1, 1) (isotropic); every component finite and > 0;
+ *           a pitch with apply_2d is an error (watershed.py:152).
+ *   d2(v)   the minimum over the object voxels q of v's domain of
+ *           ((fl(px dx))^2 + (fl(py dy))^2) + (fl(pz dz))^2, evaluated in float64 in exactly this
+ *           order (2-D: without the z term); an exact integer when isotropic.  A domain without
+ *           an object voxel: d2 = ((nx px)^2 + (ny py)^2) + (nz pz)^2 over the domain's axes, n
+ *           its actual (clipped) extents -- the value vigra's separableMultiDistSquared starts
+ *           background voxels with; every true d2 is smaller.
+ *   out_dev squared = 0: float32, the float32 of the float64 square root of d2 (object voxels 0):
+ *           isotropic, the correctly rounded float32 root of the integer; with a pitch at most
+ *           1 float32 ulp from the root of the exact d2.  squared != 0 (isotropic only, an error
+ *           with a pitch): uint32, d2 itself.
+ * Limits: every dimension below 2^31; isotropic, the squared extents of a domain must sum to less
+ * than 2^32 (checked on the host: error).  A shape with a zero dimension writes nothing.  Every
+ * check of the arguments precedes the first device call; invalid combinations return -1 with a
+ * message.  The input is not modified; out_dev must not overlap it. */
+int cc_distance_transform(cc_ctx* ctx, const uint8_t* objects_dev, const int64_t shape[3],
+                          const int64_t block_shape[3], int apply_2d, const double* pitch /* nullable */,
+                          int squared, void* out_dev /* float32 or uint32 */);
+
 #ifdef __cplusplus
 }
 #endif
