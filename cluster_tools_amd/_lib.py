@@ -32,7 +32,7 @@ EXPORTS = (
     'cc_comm_unique_id', 'cc_comm_create', 'cc_comm_destroy', 'cc_label_volume_sharded', 'cc_comm_info',
     'cc_label_sizes', 'cc_size_filter', 'cc_morphology', 'cc_region_features',
     'cc_region_graph', 'cc_edge_features', 'cc_label_overlaps', 'cc_max_overlaps', 'cc_affinity_features',
-    'cc_distance_transform',
+    'cc_distance_transform', 'cc_gaussian_smooth_domains', 'cc_local_maxima_seeds',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -174,6 +174,8 @@ def load(host_only=False):
         'cc_watershed_from_seeds': (I, [P, P, P, P, P, P, P, P]),
         'cc_normalize_channels': (I, [P, P, i64, P, P, I, P]),
         'cc_distance_transform': (I, [P, P, P, P, I, P, I, P]),
+        'cc_gaussian_smooth_domains': (I, [P, P, P, P, I, ctypes.c_double, P]),
+        'cc_local_maxima_seeds': (I, [P, P, P, P, I, P, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -929,6 +931,59 @@ class Context:
         _check(load().cc_distance_transform(self._h, _ptr(objects), _ptr(shape), _ptr(bs), int(bool(apply_2d)),
                                             _ptr(pitch), int(bool(squared)), _ptr(out)))
         return out
+
+    def gaussian_smooth_domains(self, x, block_shape, sigma, apply_2d=True, out=None):
+        """_make_seeds' smoothing (watershed.py:189-191) on device: gaussian_smooth_blocks' filter
+        without the normalize; apply_2d: every z-slice of every block over y, then x (no z pass),
+        else z, y, x inside each block.  x is a float32 CUDA volume; out may be x."""
+        import torch
+        assert hasattr(x, 'data_ptr') and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        shape, bs = _i64(x.shape), _i64(block_shape)
+        assert len(shape) == 3 and len(bs) == 3
+        if out is None:
+            out = torch.empty_like(x)
+        assert out.dtype == torch.float32 and out.shape == x.shape and out.is_contiguous()
+        _check(load().cc_gaussian_smooth_domains(self._h, _ptr(x), _ptr(shape), _ptr(bs), int(bool(apply_2d)),
+                                                 float(sigma), _ptr(out)))
+        return out
+
+    def local_maxima_seeds(self, values, domain_shape=None, indirect=False, out=None, return_counts=False):
+        """_make_seeds' local maxima and their labelling (watershed.py:187-206) on device, per
+        domain of domain_shape (None: the whole volume): the plateau maxima of the float32 CUDA
+        volume under the 6- (indirect: 26-) neighbourhood inside the domain, labelled with direct
+        connectivity and numbered 1 .. n_d per domain in raster order of each seed's first voxel.
+        Returns the seeds (uint64 bits in a torch int64 tensor), with return_counts also n_d per
+        domain (int64, raster order of the domain grid).  See include/cc_mi355x.h."""
+        import torch
+        assert hasattr(values, 'data_ptr') and values.is_cuda and values.dtype == torch.float32
+        assert values.dim() == 3 and values.is_contiguous()
+        shape = _i64(values.shape)
+        ds = _i64([max(1, s) for s in values.shape] if domain_shape is None else domain_shape)
+        assert len(ds) == 3
+        if out is None:
+            out = torch.empty(tuple(values.shape), dtype=torch.int64, device=values.device)
+        assert out.is_cuda and out.element_size() == 8 and out.shape == values.shape and out.is_contiguous()
+        counts = None
+        if return_counts:
+            nd = 1
+            for s, d in zip(shape, ds):
+                nd *= 0 if s == 0 or d <= 0 else -(-int(s) // min(int(d), int(s)))
+            counts = torch.zeros(nd, dtype=torch.int64, device=values.device)
+        _check(load().cc_local_maxima_seeds(self._h, _ptr(values), _ptr(shape), _ptr(ds), int(bool(indirect)),
+                                            _ptr(out), _ptr(counts)))
+        return (out, counts) if return_counts else out
+
+    def watershed_seeds(self, dt, block_shape, sigma_seeds=2., apply_2d=True):
+        """_make_seeds (watershed.py:180-208, without the non-maximum suppression) on device: the
+        distance transform is smoothed (gaussian_smooth_domains; not when sigma_seeds is 0 or
+        None), then the maxima are taken per z-slice of each block with the 8-neighbourhood
+        (apply_2d; vigranumpy's localMaxima default) or per block with the 6-neighbourhood
+        (localMaxima3D's default).  Returns (seeds, counts) as local_maxima_seeds does."""
+        by, bx = int(block_shape[1]), int(block_shape[2])
+        x = self.gaussian_smooth_domains(dt, block_shape, sigma_seeds, apply_2d=apply_2d) if sigma_seeds else dt
+        if apply_2d:
+            return self.local_maxima_seeds(x, (1, by, bx), indirect=True, return_counts=True)
+        return self.local_maxima_seeds(x, block_shape, indirect=False, return_counts=True)
 
     def evaluate(self, seg, gt, block_shape, ignore_label=0):
         """EvaluationWorkflow (evaluation/evaluation_workflow.py:46-84) on device: overlaps per

@@ -384,16 +384,23 @@ struct WinArgs {
     int64_t gz, gy, nxc;
     const NormP* np;
 };
+// norm: the z pass normalizes (cc_gaussian_smooth_blocks); two_d: no z pass, the y pass reads the
+// input (cc_gaussian_smooth_domains, per z-slice)
 template <int R>
-static void gauss_win_passes(cc_ctx* c, const WinArgs& w, const GaussTaps& tp) {
+static void gauss_win_passes(cc_ctx* c, const WinArgs& w, const GaussTaps& tp, bool norm, bool two_d) {
     hipStream_t s = cstream(c);
-    launch(c, "k_gauss_z", [&] {
-        k_gauss_win<0, R, true><<<(unsigned)w.gz, 64, 0, s>>>(w.in, w.A, w.Y, w.X, w.by, w.bx, w.nby, w.nbx, w.sz, w.Y,
-                                                              w.nxc, w.np, tp);
-    });
+    if (!two_d)
+        launch(c, "k_gauss_z", [&] {
+            if (norm)
+                k_gauss_win<0, R, true><<<(unsigned)w.gz, 64, 0, s>>>(w.in, w.A, w.Y, w.X, w.by, w.bx, w.nby, w.nbx, w.sz,
+                                                                      w.Y, w.nxc, w.np, tp);
+            else
+                k_gauss_win<0, R, false><<<(unsigned)w.gz, 64, 0, s>>>(w.in, w.A, w.Y, w.X, w.by, w.bx, w.nby, w.nbx, w.sz,
+                                                                       w.Y, w.nxc, w.np, tp);
+        });
     launch(c, "k_gauss_y", [&] {
-        k_gauss_win<1, R, false><<<(unsigned)w.gy, 64, 0, s>>>(w.A, w.B, w.Y, w.X, w.by, w.bx, w.nby, w.nbx, w.sy, w.Z,
-                                                               w.nxc, w.np, tp);
+        k_gauss_win<1, R, false><<<(unsigned)w.gy, 64, 0, s>>>(two_d ? w.in : w.A, w.B, w.Y, w.X, w.by, w.bx, w.nby, w.nbx,
+                                                               w.sy, w.Z, w.nxc, w.np, tp);
     });
 }
 
@@ -408,6 +415,93 @@ static void axis_segs(int64_t n, int64_t bs, int out_per, std::vector<AxSeg>& v)
             S.blk = (int32_t)bi;
             v.push_back(S);
         }
+    }
+}
+
+// The passes of cc_gaussian_smooth_blocks (norm: the z pass normalizes with the block statistics
+// smin / smax / sflag of nb blocks) and of cc_gaussian_smooth_domains (no statistics; two_d: the
+// z pass is skipped, every z-slice of a block filtered over y, then x).  Enqueues only.
+static void gauss_passes(cc_ctx* c, const float* in, float* out, const int64_t shape[3], const int64_t block_shape[3],
+                         const GaussTaps& tp, bool norm, bool two_d, int64_t nb, const u32* smin, const u32* smax,
+                         const u32* sflag) {
+    const int r = tp.r;
+    const int64_t Z = shape[0], Y = shape[1], X = shape[2], n = Z * Y * X;
+    const int nby = (int)((Y + block_shape[1] - 1) / block_shape[1]), nbx = (int)((X + block_shape[2] - 1) / block_shape[2]);
+    hipStream_t s = cstream(c);
+    // register-window z / y passes (k_gauss_win) when the taps fit and rows are 16-B aligned;
+    // else the LDS-staged k_gauss_zy
+    const bool win = r <= GS_WIN_RMAX && X % 4 == 0 && ((uintptr_t)in | (uintptr_t)out) % 16 == 0;
+    std::vector<AxSeg> sz, sy, sx;
+    axis_segs(Z, block_shape[0], win ? 64 : GS_ZY_OUT, sz);
+    axis_segs(Y, block_shape[1], win ? 128 : GS_ZY_OUT, sy);
+    axis_segs(X, block_shape[2], GS_X_OUT, sx);
+    CC_REQUIRE(sx.size() < 65536, "too many x segments");
+    const size_t nseg = sz.size() + sy.size() + sx.size();
+    c->gs_tab.ensure(nseg * sizeof(AxSeg) + (size_t)nb * sizeof(NormP));
+    AxSeg* dseg = c->gs_tab.as<AxSeg>();
+    NormP* np = (NormP*)(dseg + nseg);
+    static_assert(sizeof(AxSeg) % sizeof(int32_t) == 0, "AxSeg as int32 words");
+    c->h_gs.resize(nseg * sizeof(AxSeg) / sizeof(int32_t));    // kept alive until the stream has read it
+    {
+        char* h = reinterpret_cast<char*>(c->h_gs.data());
+        std::memcpy(h, sz.data(), sz.size() * sizeof(AxSeg));
+        std::memcpy(h + sz.size() * sizeof(AxSeg), sy.data(), sy.size() * sizeof(AxSeg));
+        std::memcpy(h + (sz.size() + sy.size()) * sizeof(AxSeg), sx.data(), sx.size() * sizeof(AxSeg));
+    }
+    HIP_OK(hipMemcpyAsync(dseg, c->h_gs.data(), nseg * sizeof(AxSeg), hipMemcpyHostToDevice, s));
+    if (norm) launch(c, "k_norm_params", [&] { k_norm_params<<<(unsigned)((nb + 255) / 256), 256, 0, s>>>(nb, smin, smax, sflag, np); });
+    if (!two_d) c->gs1.ensure(n * sizeof(float));
+    c->gs2.ensure(n * sizeof(float));
+    float* A = two_d ? nullptr : c->gs1.as<float>();
+    float* B = c->gs2.as<float>();
+    if (win) {
+        const int64_t nxc = (X / 4 + 63) / 64;
+        const int64_t gz = (int64_t)sz.size() * Y * nxc, gy = (int64_t)sy.size() * Z * nxc;
+        CC_REQUIRE(gz < (1ll << 31) && gy < (1ll << 31), "volume too large for the z / y pass grid");
+        const WinArgs wa{in, A, B, Y, X, Z, block_shape[1], block_shape[2], nby, nbx, dseg,
+                         dseg + sz.size(), gz, gy, nxc, np};
+        switch (r) {
+            case 1: gauss_win_passes<1>(c, wa, tp, norm, two_d); break;
+            case 2: gauss_win_passes<2>(c, wa, tp, norm, two_d); break;
+            case 3: gauss_win_passes<3>(c, wa, tp, norm, two_d); break;
+            case 4: gauss_win_passes<4>(c, wa, tp, norm, two_d); break;
+            case 5: gauss_win_passes<5>(c, wa, tp, norm, two_d); break;
+            case 6: gauss_win_passes<6>(c, wa, tp, norm, two_d); break;
+            case 7: gauss_win_passes<7>(c, wa, tp, norm, two_d); break;
+            default: gauss_win_passes<8>(c, wa, tp, norm, two_d); break;
+        }
+    } else {
+        const int64_t nxt = (X + 63) / 64;
+        const size_t lds_zy = (size_t)(GS_ZY_OUT + 2 * r) * 64 * sizeof(float);
+        const int64_t grid_z = (int64_t)sz.size() * Y * nxt, grid_y = (int64_t)sy.size() * Z * nxt;
+        CC_REQUIRE(grid_z < (1ll << 31) && grid_y < (1ll << 31), "volume too large for the z / y pass grid");
+        if (!two_d)
+            launch(c, "k_gauss_z", [&] {
+                if (norm)
+                    k_gauss_zy<0, true><<<(unsigned)grid_z, 256, lds_zy, s>>>(in, A, Z, Y, X, block_shape[1], block_shape[2],
+                                                                              nby, nbx, dseg, Y, nxt, np, tp);
+                else
+                    k_gauss_zy<0, false><<<(unsigned)grid_z, 256, lds_zy, s>>>(in, A, Z, Y, X, block_shape[1], block_shape[2],
+                                                                               nby, nbx, dseg, Y, nxt, np, tp);
+            });
+        launch(c, "k_gauss_y", [&] {
+            k_gauss_zy<1, false><<<(unsigned)grid_y, 256, lds_zy, s>>>(two_d ? in : A, B, Z, Y, X, block_shape[1], block_shape[2],
+                                                                       nby, nbx, dseg + sz.size(), Z, nxt, np, tp);
+        });
+    }
+    {
+        const int64_t rows = Z * Y, gx = (rows + 3) / 4;
+        CC_REQUIRE(gx < (1ll << 31), "volume too large for the x pass grid");
+        const size_t lds_x = (size_t)4 * (GS_X_OUT + 2 * GS_RMAX) * sizeof(float);
+        const bool x4 = X % 4 == 0 && block_shape[2] % 4 == 0 && ((uintptr_t)out % 16) == 0;
+        launch(c, "k_gauss_x", [&] {
+            if (x4)
+                k_gauss_x4<<<dim3((unsigned)gx, (unsigned)sx.size()), 256, lds_x, s>>>(B, out, rows, X,
+                                                                                    dseg + sz.size() + sy.size(), tp);
+            else
+                k_gauss_x<<<dim3((unsigned)gx, (unsigned)sx.size()), 256, lds_x, s>>>(B, out, rows, X,
+                                                                                   dseg + sz.size() + sy.size(), tp);
+        });
     }
 }
 
@@ -444,7 +538,6 @@ int cc_gaussian_smooth_blocks(cc_ctx* c, const float* in, const int64_t shape[3]
                        "sigma_prefilter: kernel longer than a block line (block extent <= 3 sigma)");
         }
         HIP_OK(hipSetDevice(c->device));
-        const int64_t Z = shape[0], Y = shape[1], X = shape[2], n = Z * Y * X;
         hipStream_t s = cstream(c);
         // block statistics (ordered min / max, NaN flag) -> normalize parameters
         RunState& st = state(c);
@@ -460,79 +553,34 @@ int cc_gaussian_smooth_blocks(cc_ctx* c, const float* in, const int64_t shape[3]
         HIP_OK(hipMemsetAsync(smin, 0xFF, nb * sizeof(u32), s));
         HIP_OK(hipMemsetAsync(smax, 0x00, 2 * nb * sizeof(u32), s));
         launch(c, "k_block_stats", [&] { k_block_stats<<<(unsigned)nt, NTHREADS, 0, s>>>(g, in, smin, smax, sflag); });
-        // register-window z / y passes (k_gauss_win) when the taps fit and rows are 16-B aligned;
-        // else the LDS-staged k_gauss_zy
-        const bool win = r <= GS_WIN_RMAX && X % 4 == 0 && ((uintptr_t)in | (uintptr_t)out) % 16 == 0;
-        std::vector<AxSeg> sz, sy, sx;
-        axis_segs(Z, block_shape[0], win ? 64 : GS_ZY_OUT, sz);
-        axis_segs(Y, block_shape[1], win ? 128 : GS_ZY_OUT, sy);
-        axis_segs(X, block_shape[2], GS_X_OUT, sx);
-        CC_REQUIRE(sx.size() < 65536, "too many x segments");
-        const size_t nseg = sz.size() + sy.size() + sx.size();
-        c->gs_tab.ensure(nseg * sizeof(AxSeg) + nb * sizeof(NormP));
-        AxSeg* dseg = c->gs_tab.as<AxSeg>();
-        NormP* np = (NormP*)(dseg + nseg);
-        static_assert(sizeof(AxSeg) % sizeof(int32_t) == 0, "AxSeg as int32 words");
-        c->h_gs.resize(nseg * sizeof(AxSeg) / sizeof(int32_t));    // kept alive until the stream has read it
-        {
-            char* h = reinterpret_cast<char*>(c->h_gs.data());
-            std::memcpy(h, sz.data(), sz.size() * sizeof(AxSeg));
-            std::memcpy(h + sz.size() * sizeof(AxSeg), sy.data(), sy.size() * sizeof(AxSeg));
-            std::memcpy(h + (sz.size() + sy.size()) * sizeof(AxSeg), sx.data(), sx.size() * sizeof(AxSeg));
-        }
-        HIP_OK(hipMemcpyAsync(dseg, c->h_gs.data(), nseg * sizeof(AxSeg), hipMemcpyHostToDevice, s));
-        launch(c, "k_norm_params", [&] { k_norm_params<<<(unsigned)((nb + 255) / 256), 256, 0, s>>>(nb, smin, smax, sflag, np); });
-        c->gs1.ensure(n * sizeof(float));
-        c->gs2.ensure(n * sizeof(float));
-        float* A = c->gs1.as<float>();
-        float* B = c->gs2.as<float>();
-        const int nby = (int)g.nb[1], nbx = (int)g.nb[2];
-        if (win) {
-            const int64_t nxc = (X / 4 + 63) / 64;
-            const int64_t gz = (int64_t)sz.size() * Y * nxc, gy = (int64_t)sy.size() * Z * nxc;
-            CC_REQUIRE(gz < (1ll << 31) && gy < (1ll << 31), "volume too large for the z / y pass grid");
-            const WinArgs wa{in, A, B, Y, X, Z, block_shape[1], block_shape[2], nby, nbx, dseg,
-                             dseg + sz.size(), gz, gy, nxc, np};
-            switch (r) {
-                case 1: gauss_win_passes<1>(c, wa, tp); break;
-                case 2: gauss_win_passes<2>(c, wa, tp); break;
-                case 3: gauss_win_passes<3>(c, wa, tp); break;
-                case 4: gauss_win_passes<4>(c, wa, tp); break;
-                case 5: gauss_win_passes<5>(c, wa, tp); break;
-                case 6: gauss_win_passes<6>(c, wa, tp); break;
-                case 7: gauss_win_passes<7>(c, wa, tp); break;
-                default: gauss_win_passes<8>(c, wa, tp); break;
-            }
-        } else {
-            const int64_t nxt = (X + 63) / 64;
-            const size_t lds_zy = (size_t)(GS_ZY_OUT + 2 * r) * 64 * sizeof(float);
-            const int64_t grid_z = (int64_t)sz.size() * Y * nxt, grid_y = (int64_t)sy.size() * Z * nxt;
-            CC_REQUIRE(grid_z < (1ll << 31) && grid_y < (1ll << 31), "volume too large for the z / y pass grid");
-            launch(c, "k_gauss_z", [&] {
-                k_gauss_zy<0, true><<<(unsigned)grid_z, 256, lds_zy, s>>>(in, A, Z, Y, X, block_shape[1], block_shape[2],
-                                                                          nby, nbx, dseg, Y, nxt, np, tp);
-            });
-            launch(c, "k_gauss_y", [&] {
-                k_gauss_zy<1, false><<<(unsigned)grid_y, 256, lds_zy, s>>>(A, B, Z, Y, X, block_shape[1], block_shape[2],
-                                                                           nby, nbx, dseg + sz.size(), Z, nxt, np, tp);
-            });
-        }
-        {
-            const int64_t rows = Z * Y, gx = (rows + 3) / 4;
-            CC_REQUIRE(gx < (1ll << 31), "volume too large for the x pass grid");
-            const size_t lds_x = (size_t)4 * (GS_X_OUT + 2 * GS_RMAX) * sizeof(float);
-            const bool x4 = X % 4 == 0 && block_shape[2] % 4 == 0 && ((uintptr_t)out % 16) == 0;
-            launch(c, "k_gauss_x", [&] {
-                if (x4)
-                    k_gauss_x4<<<dim3((unsigned)gx, (unsigned)sx.size()), 256, lds_x, s>>>(B, out, rows, X,
-                                                                                        dseg + sz.size() + sy.size(), tp);
-                else
-                    k_gauss_x<<<dim3((unsigned)gx, (unsigned)sx.size()), 256, lds_x, s>>>(B, out, rows, X,
-                                                                                       dseg + sz.size() + sy.size(), tp);
-            });
-        }
+        gauss_passes(c, in, out, shape, block_shape, tp, true, false, nb, smin, smax, sflag);
         sync(c);
         st.stage = 0;
+    });
+}
+
+// _make_seeds' smoothing (watershed.py:189-191: gaussianSmoothing of the distance transform, no
+// normalize, 2-D on a z-slice of the block by default): the same taps, border, sums and axis
+// order, without the statistics; apply_2d skips the z pass, so the z extent may be anything >= 1.
+int cc_gaussian_smooth_domains(cc_ctx* c, const float* in, const int64_t shape[3], const int64_t block_shape[3],
+                               int apply_2d, double sigma, float* out) {
+    CC_TRY({
+        CC_REQUIRE(c && in && out && shape && block_shape, "NULL argument");
+        CC_REQUIRE(sigma > 0, "sigma must be > 0");
+        GaussTaps tp;
+        const int r = gauss_taps(sigma, tp);
+        CC_REQUIRE(r > 0, "sigma too large (kernel radius > 64)");
+        for (int a = 0; a < 3; ++a) {
+            CC_REQUIRE(shape[a] >= 1 && block_shape[a] >= 1, "bad shape / block_shape");
+            CC_REQUIRE(shape[a] < (1ll << 31), "axis too long");
+            if (a == 0 && apply_2d) continue;
+            const int64_t last = shape[a] - (shape[a] - 1) / block_shape[a] * block_shape[a];
+            CC_REQUIRE(std::min(block_shape[a], shape[a]) > r && last > r,
+                       "gaussian_smooth_domains: kernel longer than a block line (block extent <= 3 sigma)");
+        }
+        HIP_OK(hipSetDevice(c->device));
+        gauss_passes(c, in, out, shape, block_shape, tp, false, apply_2d != 0, 0, nullptr, nullptr, nullptr);
+        sync(c);
     });
 }
 

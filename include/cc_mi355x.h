@@ -149,6 +149,15 @@ int cc_channel_mean(cc_ctx* ctx, const void* in_dev, int dtype, const int64_t sh
 int cc_gaussian_smooth_blocks(cc_ctx* ctx, const float* in_dev, const int64_t shape[3],
                               const int64_t block_shape[3], double sigma, float* out_dev);
 int cc_gaussian_taps(double sigma, float* taps, int cap);
+/* The smoothing of _make_seeds (watershed/watershed.py:189-191: gaussianSmoothing of the distance
+ * transform): the filter above -- the same taps, reflected block borders, float32 sums without FMA,
+ * axis order and error rules -- without the normalize.  apply_2d != 0: every z-slice of every block
+ * is filtered over y, then x (no z pass; the z extent may be anything >= 1); apply_2d = 0: z, y,
+ * x inside each block.  Error when a y or x block line (a z line too in 3-D mode), clipped last
+ * blocks included, is not longer than the radius.  in_dev and out_dev may alias.  Parity with
+ * vigra unpinned. */
+int cc_gaussian_smooth_domains(cc_ctx* ctx, const float* in_dev, const int64_t shape[3],
+                               const int64_t block_shape[3], int apply_2d, double sigma, float* out_dev);
 
 /* Masks of another shape than the volume (block_components.py:274-275 -> volume_utils.py:174-184:
  * elf ResizedVolume(mask, shape, order=0)): out_dev = rows z0 .. z0 + nz of the mask resized to
@@ -603,6 +612,36 @@ int cc_normalize_channels(cc_ctx* ctx, const float* in_dev, int64_t n_channels, 
 int cc_distance_transform(cc_ctx* ctx, const uint8_t* objects_dev, const int64_t shape[3],
                           const int64_t block_shape[3], int apply_2d, const double* pitch /* nullable */,
                           int squared, void* out_dev /* float32 or uint32 */);
+
+/* --- Seeds of the distance-transform watershed: local maxima with plateaus, per domain ---
+ * The second stage of the reference's distance-transform watershed after its smoothing
+ * (_make_seeds, watershed/watershed.py:187-206: vigra.analysis.localMaxima / localMaxima3D with
+ * allowAtBorder = allowPlateaus = True, the "just one plateau" branch, then
+ * labelMultiArrayWithBackground).  vigra is absent here: what follows is the definition, parity
+ * with vigra is unpinned.  values_dev holds shape[0] x shape[1] x shape[2] (z, y, x) float32.
+ *   domains the volume is cut from the origin with domain_shape, the last domain per axis clipped;
+ *           domains are independent (no voxel sees a voxel of another domain).  The reference's
+ *           per-slice mode is domain_shape = (1, by, bx).  Domain index: raster order of the domain
+ *           grid, z slowest.
+ *   N       indirect = 0: the 6 face neighbours (4 within a slice); indirect != 0: all 26 (8
+ *           within a slice); only neighbours inside the domain count (allowAtBorder).
+ *   maxima  all comparisons IEEE float32 (-0.0 == 0.0; +inf plateaus are ordinary).  A voxel v is
+ *           a candidate iff f(v) >= f(u) for every neighbour u: a NaN voxel with neighbours is
+ *           never one, nor are its neighbours; two neighbouring candidates hold equal values.  A
+ *           connected component (under N) of candidates is a maximum iff none of its voxels has a
+ *           non-candidate neighbour u with f(u) == f(v) -- a connected set of equal values all of
+ *           whose outside neighbours are strictly lower.
+ *   seeds   the maxima mask is labelled with direct connectivity (6 or 4) whatever N is: with
+ *           indirect, a plateau connected only diagonally becomes several seeds.  Inside each
+ *           domain the seeds are numbered 1 .. n_d in raster order of each component's first
+ *           voxel; every other voxel is 0.  counts_dev[d] = n_d (optional).  A constant domain
+ *           comes out all 1 with n_d = 1 (the reference's "just one plateau").
+ * Limits: every dimension below 2^31, a domain holds fewer than 2^32 voxels.  A shape with a zero
+ * dimension writes nothing.  Every check of the arguments precedes the first device call; invalid
+ * arguments return -1 with a message.  The input is not modified; seeds_dev must not overlap it. */
+int cc_local_maxima_seeds(cc_ctx* ctx, const float* values_dev, const int64_t shape[3],
+                          const int64_t domain_shape[3], int indirect, uint64_t* seeds_dev,
+                          uint64_t* counts_dev /* nullable */);
 
 #ifdef __cplusplus
 }
