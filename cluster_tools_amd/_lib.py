@@ -264,6 +264,59 @@ def _ptr(a):
     return a.ctypes.data
 
 
+def _sized_call(attempt, cap_hint, n_caps=1):
+    """The host half of a table pass ('The table pass'): attempt(*caps) allocates host
+    buffers of `caps` entries, makes the C call and returns (rc, counts, result) -- counts: the
+    entries the device reported, one per capacity.  The first attempt is at max(1, cap_hint); when a
+    count exceeds its capacity the C entry has filled nothing, and one more attempt follows with
+    that capacity at exactly the count.  Returns (rc, result); a non-zero rc comes back at once."""
+    caps = [max(1, int(cap_hint))] * n_caps
+    while True:
+        rc, counts, result = attempt(*caps)
+        if rc != 0:
+            return rc, None
+        short = False
+        for i, n in enumerate(counts):
+            if int(n) <= caps[i]:
+                continue
+            caps[i], short = int(n), True
+        if not short:
+            return 0, result
+
+
+def _relabel_retry(call, labels, names, relabel):
+    """call(labels) -> (rc, dict) for the entries whose keys pack ids: on CC_ERR_ID_RANGE the
+    volume is relabelled consecutively (relabel: Context.relabel_consecutive), the call made again
+    and the arrays `names` of its result mapped back through the table (monotone: the order
+    stays).  Any other code goes through _check."""
+    rc, out = call(labels)
+    if rc == 0:
+        return out
+    if rc != CC_ERR_ID_RANGE:
+        _check(rc)
+    relabelled, table = relabel(labels)
+    rc, out = call(relabelled)
+    _check(rc)
+    first = table[0, 1] if len(table) else np.uint64(0)
+    for k in names:
+        out[k] = table[(out[k] - first).astype(np.int64), 0]
+    return out
+
+
+def _beyond(a, limit):
+    """whether the 64-bit tensor `a`, read as unsigned, holds an id >= limit"""
+    import torch
+    v = a.view(torch.int64)
+    return bool((v < 0).any()) or bool((v >= limit).any())
+
+
+def _ignore_in(table, ignore_label):
+    """the ignore label in the new id space of a relabel table (an unused id if absent)"""
+    k = np.searchsorted(table[:, 0], np.uint64(ignore_label))
+    present = k < len(table) and table[k, 0] == np.uint64(ignore_label)
+    return int(table[k, 1]) if present else int(table[-1, 1]) + 1
+
+
 def mode_id(mode):
     if isinstance(mode, int):
         return mode
@@ -1018,18 +1071,13 @@ class Context:
         if rc != CC_ERR_ID_RANGE:                      # CC_ERR_ID_RANGE: relabel and evaluate again
             _check(rc)
 
-        def too_large(a, limit):
-            v = a.view(torch.int64)
-            return bool((v < 0).any()) or bool((v >= limit).any())
-        if too_large(seg, 2 ** 31):
+        if _beyond(seg, 2 ** 31):
             seg, self._ev_tables[0] = self.relabel_consecutive(seg)
-        if too_large(gt, 2 ** 32 - 1):
+        if _beyond(gt, 2 ** 32 - 1):
             gt, table = self.relabel_consecutive(gt)
             self._ev_tables[1] = table
-            if use_ignore:       # the ignore label in the new id space (an unused id if absent)
-                k = np.searchsorted(table[:, 0], np.uint64(ignore_label))
-                present = k < len(table) and table[k, 0] == np.uint64(ignore_label)
-                ignore_label = int(table[k, 1]) if present else int(table[-1, 1]) + 1
+            if use_ignore:
+                ignore_label = _ignore_in(table, ignore_label)
         torch.cuda.current_stream(seg.device).synchronize()
         _check(load().cc_evaluate(self._h, _ptr(seg), _ptr(gt), _ptr(shape), _ptr(bs), int(use_ignore),
                                   int(ignore_label) if use_ignore else 0, ctypes.byref(res)))
@@ -1069,30 +1117,23 @@ class Context:
 
         def call(w, lab, ignore):
             nn = np.zeros(1, dtype=np.uint64)
-            cap = max(1, int(cap_hint))
-            while True:
+
+            def attempt(cap):
                 out = {k: np.empty(cap, dtype=np.uint64) for k in LABEL_OVERLAPS}
                 rc = L.cc_label_overlaps(self._h, _ptr(w), _ptr(lab), lab.element_size(), _ptr(shape), _ptr(bs),
                                          int(use_ignore), int(ignore) if use_ignore else 0, _ptr(nn),
                                          _ptr(out['ws_ids']), _ptr(out['label_ids']), _ptr(out['counts']), cap)
-                if rc != 0:
-                    return rc, None
-                if int(nn[0]) <= cap:
-                    break
-                cap = int(nn[0])
-            return 0, {k: v[:int(nn[0])].copy() for k, v in out.items()}
+                return rc, nn, out
+            rc, out = _sized_call(attempt, cap_hint)
+            return (rc, None) if rc else (0, {k: v[:int(nn[0])].copy() for k, v in out.items()})
 
         rc, table = call(ws, labels, ignore_label)
         if rc == 0:
             return table, True
         if rc != CC_ERR_ID_RANGE:                      # CC_ERR_ID_RANGE: relabel and call again
             _check(rc)
-
-        def too_large(a, limit):
-            v = a.view(torch.int64)
-            return bool((v < 0).any()) or bool((v >= limit).any())
         maps = {}
-        if too_large(ws, 2 ** 31):
+        if _beyond(ws, 2 ** 31):
             ws, maps['ws_ids'] = self.relabel_consecutive(ws)
         if elem == 4:                                  # only 2^32 - 1 is beyond the packing: widened, then as uint64
             wide = labels.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
@@ -1100,13 +1141,11 @@ class Context:
             wide = labels
         else:
             wide = None
-        if wide is not None and too_large(wide, 2 ** 32 - 1):
+        if wide is not None and _beyond(wide, 2 ** 32 - 1):
             labels, table = self.relabel_consecutive(wide)
             maps['label_ids'] = table
-            if use_ignore:       # the ignore label in the new id space (an unused id if absent)
-                k = np.searchsorted(table[:, 0], np.uint64(ignore_label))
-                present = k < len(table) and table[k, 0] == np.uint64(ignore_label)
-                ignore_label = int(table[k, 1]) if present else int(table[-1, 1]) + 1
+            if use_ignore:
+                ignore_label = _ignore_in(table, ignore_label)
         torch.cuda.current_stream(ws.device).synchronize()
         rc, table = call(ws, labels, ignore_label)
         _check(rc)
@@ -1174,24 +1213,21 @@ class Context:
         expected number of distinct ids (sizes the host table and the device id set; a larger
         count costs a second call)."""
         import torch
-        assert hasattr(labels, 'data_ptr') and labels.is_cuda and labels.element_size() == 8
-        assert labels.is_contiguous() and labels.dtype in (torch.int64, torch.uint64)
+        self._check_labels(labels)
         if out is None:
             out = torch.empty_like(labels)
         assert out.shape == labels.shape and out.is_contiguous() and out.element_size() == 8
-        torch.cuda.current_stream(labels.device).synchronize()
         L = load()
         nu, st = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
-        cap = max(1, int(cap_hint))
-        while True:
+
+        def attempt(cap):
             # a table larger than cap is reported (n_unique) before out is touched, so in-place
             # calls are safe: the second call has the exact size
             uniq = np.empty(cap, dtype=np.uint64)
-            _check(L.cc_relabel_consecutive(self._h, _ptr(labels), _ptr(out), labels.numel(), _ptr(nu), _ptr(st),
-                                            _ptr(uniq), cap))
-            if int(nu[0]) <= cap:
-                break
-            cap = int(nu[0])
+            return L.cc_relabel_consecutive(self._h, _ptr(labels), _ptr(out), labels.numel(), _ptr(nu), _ptr(st),
+                                            _ptr(uniq), cap), nu, uniq
+        rc, uniq = _sized_call(attempt, cap_hint)
+        _check(rc)
         n = int(nu[0])
         uniq = uniq[:n]
         table = np.stack([uniq, np.arange(int(st[0]), int(st[0]) + n, dtype=np.uint64)], axis=1)
@@ -1204,6 +1240,20 @@ class Context:
         assert labels.is_contiguous() and labels.dtype in (torch.int64, torch.uint64)
         torch.cuda.current_stream(labels.device).synchronize()
 
+    @staticmethod
+    def _check_values(values, labels, same_shape):
+        """the float32 / uint8 operand of region_features and edge_features; whether it is uint8"""
+        import torch
+        assert hasattr(values, 'data_ptr') and values.is_cuda and values.is_contiguous(), \
+            'values must be a contiguous CUDA tensor'
+        assert values.dtype in (torch.float32, torch.uint8), 'values must be float32 or uint8'
+        if same_shape:
+            assert tuple(values.shape) == tuple(labels.shape), 'labels and values must have the same shape'
+        else:
+            assert values.numel() == labels.numel(), 'labels and values must have the same number of elements'
+        assert values.device == labels.device
+        return values.dtype == torch.uint8
+
     def label_sizes(self, labels, cap_hint=1 << 20):
         """FindUniques(return_counts=True) (relabel/find_uniques.py:105-179) over the whole volume
         on device: returns (ids, counts), the sorted distinct ids of the uint64 (torch int64 /
@@ -1213,15 +1263,15 @@ class Context:
         self._check_labels(labels)
         L = load()
         nu = np.zeros(1, dtype=np.uint64)
-        cap = max(1, int(cap_hint))
-        while True:
+
+        def attempt(cap):
             ids, counts = np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
-            _check(L.cc_label_sizes(self._h, _ptr(labels), labels.numel(), _ptr(nu), _ptr(ids), _ptr(counts), cap))
-            if int(nu[0]) <= cap:
-                break
-            cap = int(nu[0])
+            return (L.cc_label_sizes(self._h, _ptr(labels), labels.numel(), _ptr(nu), _ptr(ids), _ptr(counts), cap),
+                    nu, (ids, counts))
+        rc, bufs = _sized_call(attempt, cap_hint)
+        _check(rc)
         n = int(nu[0])
-        return ids[:n].copy(), counts[:n].copy()
+        return bufs[0][:n].copy(), bufs[1][:n].copy()
 
     def morphology(self, labels, origin=(0, 0, 0), cap_hint=1 << 20, raw=False):
         """MorphologyWorkflow (morphology/morphology_workflow.py:11-56) over the whole volume on
@@ -1239,13 +1289,12 @@ class Context:
         assert org.shape == (3,)
         L = load()
         nu = np.zeros(1, dtype=np.uint64)
-        cap = max(1, int(cap_hint))
-        while True:
+
+        def attempt(cap):
             rows = np.empty((cap, MORPHOLOGY_COLUMNS), dtype=np.uint64)
-            _check(L.cc_morphology(self._h, _ptr(labels), _ptr(shape), _ptr(org), _ptr(nu), _ptr(rows), cap))
-            if int(nu[0]) <= cap:
-                break
-            cap = int(nu[0])
+            return L.cc_morphology(self._h, _ptr(labels), _ptr(shape), _ptr(org), _ptr(nu), _ptr(rows), cap), nu, rows
+        rc, rows = _sized_call(attempt, cap_hint)
+        _check(rc)
         rows = rows[:int(nu[0])].copy()
         return rows if raw else _morphology_float(rows)
 
@@ -1262,25 +1311,18 @@ class Context:
         / 255.  An id that holds a NaN has a NaN sum, minimum and maximum; no other id is
         affected.  cap_hint: the expected number of distinct ids (a larger count costs a second
         call)."""
-        import torch
         self._check_labels(labels)
-        assert hasattr(values, 'data_ptr') and values.is_cuda and values.is_contiguous(), \
-            'values must be a contiguous CUDA tensor'
-        assert values.dtype in (torch.float32, torch.uint8), 'values must be float32 or uint8'
-        assert values.numel() == labels.numel(), 'labels and values must have the same number of elements'
-        assert values.device == labels.device
-        u8 = values.dtype == torch.uint8
+        u8 = self._check_values(values, labels, same_shape=False)
         L = load()
         nu = np.zeros(1, dtype=np.uint64)
-        cap = max(1, int(cap_hint))
-        while True:
+
+        def attempt(cap):
             out = {k: np.empty(cap, dtype=t) for k, t in RAW_REGION_FEATURES}
-            _check(L.cc_region_features(self._h, _ptr(labels), _ptr(values), 1 if u8 else 0, labels.numel(), _ptr(nu),
+            return L.cc_region_features(self._h, _ptr(labels), _ptr(values), 1 if u8 else 0, labels.numel(), _ptr(nu),
                                         _ptr(out['ids']), _ptr(out['count']), _ptr(out['sum']), _ptr(out['minimum']),
-                                        _ptr(out['maximum']), cap))
-            if int(nu[0]) <= cap:
-                break
-            cap = int(nu[0])
+                                        _ptr(out['maximum']), cap), nu, out
+        rc, out = _sized_call(attempt, cap_hint)
+        _check(rc)
         out = {k: v[:int(nu[0])].copy() for k, v in out.items()}
         return out if raw else _region_features_float(out, u8)
 
@@ -1310,32 +1352,20 @@ class Context:
 
         def call(lab):
             nn, ne = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
-            ncap = ecap = max(1, int(cap_hint))
-            while True:
+
+            def attempt(ncap, ecap):
                 nodes, edges, sizes = (np.empty(ncap, dtype=np.uint64), np.empty((ecap, 2), dtype=np.uint64),
                                        np.empty(ecap, dtype=np.uint64))
                 rc = L.cc_region_graph(self._h, _ptr(lab), _ptr(shape), _ptr(own), int(bool(ignore_label)), _ptr(nn),
                                        _ptr(nodes), ncap, _ptr(ne), _ptr(edges), _ptr(sizes), ecap)
-                if rc != 0:
-                    return rc, None
-                if int(nn[0]) <= ncap and int(ne[0]) <= ecap:
-                    break
-                ncap, ecap = max(ncap, int(nn[0])), max(ecap, int(ne[0]))
+                return rc, (nn[0], ne[0]), (nodes, edges, sizes)
+            rc, bufs = _sized_call(attempt, cap_hint, n_caps=2)
+            if rc != 0:
+                return rc, None
             n, m = int(nn[0]), int(ne[0])
-            return 0, {'nodes': nodes[:n].copy(), 'edges': edges[:m].copy(), 'sizes': sizes[:m].copy()}
+            return 0, {'nodes': bufs[0][:n].copy(), 'edges': bufs[1][:m].copy(), 'sizes': bufs[2][:m].copy()}
 
-        rc, graph = call(labels)
-        if rc == 0:
-            return graph
-        if rc != CC_ERR_ID_RANGE:                      # CC_ERR_ID_RANGE: relabel and call again
-            _check(rc)
-        relabelled, table = self.relabel_consecutive(labels)
-        rc, graph = call(relabelled)
-        _check(rc)
-        first = table[0, 1] if len(table) else np.uint64(0)
-        for k in ('nodes', 'edges'):                   # back from the relabelled id space
-            graph[k] = table[(graph[k] - first).astype(np.int64), 0]
-        return graph
+        return _relabel_retry(call, labels, ('nodes', 'edges'), self.relabel_consecutive)
 
     def edge_features(self, labels, values, ignore_label=True, owned=None, cap_hint=1 << 20, raw=False):
         """EdgeFeaturesWorkflow for boundary maps (features/features_workflow.py:12-64) over the
@@ -1359,53 +1389,52 @@ class Context:
         count costs a second call).  Ids >= 2^32 - 1: as region_graph (relabelled on the device,
         edges mapped back).  Affinity maps with offsets: affinity_features.  Filter responses are
         not built."""
-        import torch
         self._check_labels(labels)
         assert labels.dim() == 3, 'labels must be 3-D (z, y, x)'
-        assert hasattr(values, 'data_ptr') and values.is_cuda and values.is_contiguous(), \
-            'values must be a contiguous CUDA tensor'
-        assert values.dtype in (torch.float32, torch.uint8), 'values must be float32 or uint8'
-        assert tuple(values.shape) == tuple(labels.shape), 'labels and values must have the same shape'
-        assert values.device == labels.device
+        u8 = self._check_values(values, labels, same_shape=True)
         shape = _i64(labels.shape)
         own = shape if owned is None else _i64(owned)
         assert own.shape == (3,) and (own >= 0).all() and (own <= shape).all(), 'owned must lie within labels.shape'
-        u8 = values.dtype == torch.uint8
         L = load()
 
+        def entry(lab, *out):
+            return L.cc_edge_features(self._h, _ptr(lab), _ptr(values), 1 if u8 else 0, _ptr(shape), _ptr(own),
+                                      int(bool(ignore_label)), *out)
+        return self._edge_features(entry, labels, u8, cap_hint, raw)
+
+    def _edge_features(self, entry, labels, u8, cap_hint, raw, extra=()):
+        """edge_features and affinity_features behind their operand checks: the host buffers, the
+        retries and the result.  entry(labels, n_edges, edges, count, sum, sumsq, minimum, maximum,
+        quantiles, hist, cap): the C entry after its own leading arguments; extra: further
+        (key, value) fields of the raw table."""
+        quant = None
+
         def call(lab):
+            nonlocal quant
             ne = np.zeros(1, dtype=np.uint64)
-            cap = max(1, int(cap_hint))
-            while True:
+
+            def attempt(cap):
                 out = {k: np.empty(cap, dtype=t) for k, t in RAW_EDGE_FEATURES}
-                edges, quant = np.empty((cap, 2), dtype=np.uint64), np.empty((cap, len(EDGE_QUANTILES)), dtype=np.float64)
+                edges, q = np.empty((cap, 2), dtype=np.uint64), np.empty((cap, len(EDGE_QUANTILES)), dtype=np.float64)
                 hist = np.empty((cap, EDGE_BINS), dtype=np.uint32) if raw else None
-                rc = L.cc_edge_features(self._h, _ptr(lab), _ptr(values), 1 if u8 else 0, _ptr(shape), _ptr(own),
-                                        int(bool(ignore_label)), _ptr(ne), _ptr(edges), _ptr(out['count']),
-                                        _ptr(out['sum']), _ptr(out['sumsq']), _ptr(out['minimum']), _ptr(out['maximum']),
-                                        _ptr(quant), _ptr(hist) if raw else None, cap)
-                if rc != 0:
-                    return rc, None, None
-                if int(ne[0]) <= cap:
-                    break
-                cap = int(ne[0])
+                rc = entry(lab, _ptr(ne), _ptr(edges), _ptr(out['count']), _ptr(out['sum']), _ptr(out['sumsq']),
+                           _ptr(out['minimum']), _ptr(out['maximum']), _ptr(q), _ptr(hist) if raw else None, cap)
+                return rc, ne, (out, edges, q, hist)
+            rc, bufs = _sized_call(attempt, cap_hint)
+            if rc != 0:
+                return rc, None
+            out, edges, q, hist = bufs
             m = int(ne[0])
             out = {k: v[:m].copy() for k, v in out.items()}
             out['edges'] = edges[:m].copy()
             out['uint8_input'] = u8
+            out.update(extra)
             if raw:
                 out['hist'] = hist[:m].copy()
-            return 0, out, quant[:m]
+            quant = q[:m]
+            return 0, out
 
-        rc, out, quant = call(labels)
-        if rc != 0:
-            if rc != CC_ERR_ID_RANGE:                  # CC_ERR_ID_RANGE: relabel and call again
-                _check(rc)
-            relabelled, table = self.relabel_consecutive(labels)
-            rc, out, quant = call(relabelled)
-            _check(rc)
-            first = table[0, 1] if len(table) else np.uint64(0)
-            out['edges'] = table[(out['edges'] - first).astype(np.int64), 0]   # monotone: the order stays
+        out = _relabel_retry(call, labels, ('edges',), self.relabel_consecutive)
         if raw:
             return out
         return {'edges': out['edges'], 'features': _edge_features_columns(out, quant)}
@@ -1448,43 +1477,10 @@ class Context:
         u8 = affinities.dtype == torch.uint8
         L = load()
 
-        def call(lab):
-            ne = np.zeros(1, dtype=np.uint64)
-            cap = max(1, int(cap_hint))
-            while True:
-                out = {k: np.empty(cap, dtype=t) for k, t in RAW_EDGE_FEATURES}
-                edges, quant = np.empty((cap, 2), dtype=np.uint64), np.empty((cap, len(EDGE_QUANTILES)), dtype=np.float64)
-                hist = np.empty((cap, EDGE_BINS), dtype=np.uint32) if raw else None
-                rc = L.cc_affinity_features(self._h, _ptr(lab), _ptr(affinities), 1 if u8 else 0, _ptr(shape), len(offs),
-                                            _ptr(offs), int(bool(ignore_label)), _ptr(ne), _ptr(edges), _ptr(out['count']),
-                                            _ptr(out['sum']), _ptr(out['sumsq']), _ptr(out['minimum']),
-                                            _ptr(out['maximum']), _ptr(quant), _ptr(hist) if raw else None, cap)
-                if rc != 0:
-                    return rc, None, None
-                if int(ne[0]) <= cap:
-                    break
-                cap = int(ne[0])
-            m = int(ne[0])
-            out = {k: v[:m].copy() for k, v in out.items()}
-            out['edges'] = edges[:m].copy()
-            out['uint8_input'] = u8
-            out['offsets'] = offs.copy()
-            if raw:
-                out['hist'] = hist[:m].copy()
-            return 0, out, quant[:m]
-
-        rc, out, quant = call(labels)
-        if rc != 0:
-            if rc != CC_ERR_ID_RANGE:                  # CC_ERR_ID_RANGE: relabel and call again
-                _check(rc)
-            relabelled, table = self.relabel_consecutive(labels)
-            rc, out, quant = call(relabelled)
-            _check(rc)
-            first = table[0, 1] if len(table) else np.uint64(0)
-            out['edges'] = table[(out['edges'] - first).astype(np.int64), 0]   # monotone: the order stays
-        if raw:
-            return out
-        return {'edges': out['edges'], 'features': _edge_features_columns(out, quant)}
+        def entry(lab, *out):
+            return L.cc_affinity_features(self._h, _ptr(lab), _ptr(affinities), 1 if u8 else 0, _ptr(shape), len(offs),
+                                          _ptr(offs), int(bool(ignore_label)), *out)
+        return self._edge_features(entry, labels, u8, cap_hint, raw, extra={'offsets': offs.copy()})
 
     def size_filter(self, labels, size_threshold=None, target_number=None, discard_ids=None, relabel=True,
                     out=None, cap_hint=1 << 20):
@@ -1517,19 +1513,19 @@ class Context:
         assert 0 <= value < 1 << 64
         L = load()
         res = CCSizeFilterResult()
-        cap = max(1, int(cap_hint))
-        while True:
+
+        def attempt(cap):
             # a table larger than cap is reported (n_unique) before out is touched, so in-place
             # calls are safe: the second call has the exact size
-            ids, counts, new = (np.empty(cap, dtype=np.uint64) for _ in range(3))
-            _check(L.cc_size_filter(self._h, _ptr(labels), _ptr(out), labels.numel(), sel, value, _ptr(dis),
-                                    0 if dis is None else len(dis), 1 if relabel else 0, ctypes.byref(res),
-                                    _ptr(ids), _ptr(counts), _ptr(new), cap))
-            if int(res.n_unique) <= cap:
-                break
-            cap = int(res.n_unique)
+            bufs = [np.empty(cap, dtype=np.uint64) for _ in range(3)]
+            rc = L.cc_size_filter(self._h, _ptr(labels), _ptr(out), labels.numel(), sel, value, _ptr(dis),
+                                  0 if dis is None else len(dis), 1 if relabel else 0, ctypes.byref(res),
+                                  _ptr(bufs[0]), _ptr(bufs[1]), _ptr(bufs[2]), cap)
+            return rc, (res.n_unique,), bufs
+        rc, bufs = _sized_call(attempt, cap_hint)
+        _check(rc)
         n = int(res.n_unique)
-        ids, counts, new = ids[:n].copy(), counts[:n].copy(), new[:n].copy()
+        ids, counts, new = (b[:n].copy() for b in bufs)
         info = res.as_dict()
         kept = new != 0                                # kept non-zero ids (their output value is >= 1)
         table = np.stack([ids[kept], new[kept]], axis=1)

@@ -27,6 +27,7 @@ __global__ __launch_bounds__(NTHREADS) void k_block_stats(Geom g, const float* _
 }  // namespace aux
 }  // namespace cc
 
+#include "cc_table_pass.hpp"
 #include "cc_eval.hip"
 #include "cc_node_labels.hip"
 #include "cc_relabel.hip"

@@ -62,6 +62,19 @@ __device__ bool ev_insert(u64* keys, u64* cnts, u64 mask, u64 key, u64 c) {
     return false;
 }
 
+// the occupied slots of a (keys, counts) table, in any order (a sort follows); *count = their
+// number.  The node labels' and the size filter's compaction (k_nl_compact / k_sf_compact in a profile)
+__global__ __launch_bounds__(256) void k_tab_compact(const u64* __restrict__ keys, const u64* __restrict__ cnts, u64 cap,
+                                                     u64* out_keys, u64* out_cnts, u32* count) {
+    for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < cap; e += (u64)gridDim.x * 256) {
+        const u64 k = keys[e];
+        if (k == EV_EMPTY) continue;
+        const u32 at = atomicAdd(count, 1u);
+        out_keys[at] = k;
+        out_cnts[at] = cnts[e];
+    }
+}
+
 struct EvTabs {
     u64 *mk, *mc;   // pairs (seg << 32 | gt)
     u64 *zk, *zc;   // seg-0 pairs per block
@@ -314,70 +327,59 @@ static int evaluate_impl(cc_ctx* c, const uint64_t* seg, const uint64_t* gt, con
         const unsigned grid = (unsigned)n_wg;
         c->ev_flag.ensure(n_blocks * sizeof(u32) + 16);
         c->ev_part.ensure(4 * EV_REDUCE_WG * sizeof(u64));
-        c->counter.ensure(sizeof(u32));
+        u64* pu = c->ev_part.as<u64>();
+        double* pf = (double*)(pu + 2 * EV_REDUCE_WG);
+        u64 *mk = nullptr, *sk = nullptr, *gk = nullptr;
+        EvSums m{};
         // 2^20 slots (16 MB per table) to start: C3-sized partitions hold ~150 k pairs, and a table
         // that fills up costs a slow pass plus a rerun (the 80 ms first call of round 2)
-        int64_t cap = std::max<int64_t>(c->ev_cap, 1 << 20);
-        for (;;) {
+        const int64_t cap = table_pass(c->ev_cap, 1 << 20, 0, "contingency table larger than 2^30 pairs", [&](int64_t cap) {
             c->ev_main.ensure(2 * cap * sizeof(u64));
             c->ev_z.ensure(2 * cap * sizeof(u64));
             c->ev_seg.ensure(2 * cap * sizeof(u64));
             c->ev_gt.ensure(2 * cap * sizeof(u64));
-            u64* mk = c->ev_main.as<u64>();
+            mk = c->ev_main.as<u64>();
             u64* zk = c->ev_z.as<u64>();
-            u64* sk = c->ev_seg.as<u64>();
-            u64* gk = c->ev_gt.as<u64>();
-            for (u64* k : {mk, zk, sk, gk}) {
-                HIP_OK(hipMemsetAsync(k, 0xFF, cap * sizeof(u64), s));
-                HIP_OK(hipMemsetAsync(k + cap, 0, cap * sizeof(u64), s));
-            }
+            sk = c->ev_seg.as<u64>();
+            gk = c->ev_gt.as<u64>();
+            for (u64* k : {mk, zk, sk, gk}) table_clear(c, k, cap * sizeof(u64), cap * sizeof(u64));
             HIP_OK(hipMemsetAsync(c->ev_flag.p, 0, n_blocks * sizeof(u32), s));
-            HIP_OK(hipMemsetAsync(c->counter.p, 0, sizeof(u32), s));
-            EvTabs t{mk, mk + cap, zk, zk + cap, (u64)cap - 1, c->counter.as<u32>()};
+            EvTabs t{mk, mk + cap, zk, zk + cap, (u64)cap - 1, counters_clear(c, 1)};
             u32* flag = c->ev_flag.as<u32>();
             launch(c, "k_ev_overlaps", [&] {
                 k_ev_overlaps<<<grid, 256, 0, s>>>(seg, gt, n_rows, rows_per_wg, gr, use_ignore ? 1 : 0, ignore_label, t, flag);
             });
             launch(c, "k_ev_fold", [&] { k_ev_fold<<<grid_stride(cap), 256, 0, s>>>(t, flag); });
             launch(c, "k_ev_sizes", [&] { k_ev_sizes<<<std::min<unsigned>(2048, grid_stride(cap)), 256, 0, s>>>(t, sk, sk + cap, gk, gk + cap); });
-            u32 herr = 0;
-            HIP_OK(hipMemcpyAsync(&herr, c->counter.p, sizeof(u32), hipMemcpyDeviceToHost, s));
-            sync(c);
-            if (herr & EV_ERR_SEG) throw CCIdRangeError{{"segmentation id >= 2^31 (evaluation keys pack seg ids in 31 bits)"}};
-            if (herr & EV_ERR_GT) throw CCIdRangeError{{"ground-truth id >= 2^32 - 1 (evaluation keys pack gt ids in 32 bits)"}};
-            u64* pu = c->ev_part.as<u64>();
-            double* pf = (double*)(pu + 2 * EV_REDUCE_WG);
-            EvSums m{};
-            if (!(herr & EV_ERR_FULL)) m = ev_table_sums(c, mk, mk + cap, cap, pu, pf);
-            // keep every table at most half full (linear probing); grow and rerun otherwise
-            if ((herr & EV_ERR_FULL) || (int64_t)m.entries * 2 > cap) {
-                CC_REQUIRE(cap < (1LL << 31), "contingency table larger than 2^30 pairs");
-                cap *= 4;
-                continue;
-            }
-            const EvSums a = ev_table_sums(c, gk, gk + cap, cap, pu, pf);   // gt sizes (a_dict)
-            const EvSums b = ev_table_sums(c, sk, sk + cap, cap, pu, pf);   // seg sizes (b_dict)
-            c->ev_cap = cap;
-            std::memset(out, 0, sizeof(*out));
-            out->n_points = m.sum;
-            out->n_pairs = m.entries;
-            out->n_gt_ids = a.entries;
-            out->n_seg_ids = b.entries;
-            if (m.sum == 0) return 0;
-            CC_REQUIRE(a.sum == m.sum && b.sum == m.sum, "contingency table sizes disagree (measures.py:115)");
-            const double np = (double)m.sum, lg = std::log2(np);
-            // entropies in bits: H = log2(N) - (1/N) sum c log2 c
-            const double h_ab = lg - m.clog / np, h_a = lg - a.clog / np, h_b = lg - b.clog / np;
-            out->vi_split = h_ab - h_a;     // H(seg | gt)
-            out->vi_merge = h_ab - h_b;     // H(gt | seg)
-            const double prec = m.sq / b.sq, rec = m.sq / a.sq;
-            out->adapted_rand_error = 1.0 - 2.0 * prec * rec / (prec + rec);
-            out->rand_index = 1.0 - (a.sq + b.sq - 2.0 * m.sq) / (np * np);
-            out->sum_sq_pairs = m.sq;
-            out->sum_sq_gt = a.sq;
-            out->sum_sq_seg = b.sq;
-            return 0;
-        }
+            u32 herr[1] = {0};
+            counters_read(c, herr);
+            if (herr[0] & EV_ERR_SEG) throw CCIdRangeError{{"segmentation id >= 2^31 (evaluation keys pack seg ids in 31 bits)"}};
+            if (herr[0] & EV_ERR_GT) throw CCIdRangeError{{"ground-truth id >= 2^32 - 1 (evaluation keys pack gt ids in 32 bits)"}};
+            const bool full = herr[0] & EV_ERR_FULL;
+            if (!full) m = ev_table_sums(c, mk, mk + cap, cap, pu, pf);
+            return TableFill{full, (int64_t)m.entries};
+        });
+        const EvSums a = ev_table_sums(c, gk, gk + cap, cap, pu, pf);   // gt sizes (a_dict)
+        const EvSums b = ev_table_sums(c, sk, sk + cap, cap, pu, pf);   // seg sizes (b_dict)
+        std::memset(out, 0, sizeof(*out));
+        out->n_points = m.sum;
+        out->n_pairs = m.entries;
+        out->n_gt_ids = a.entries;
+        out->n_seg_ids = b.entries;
+        if (m.sum == 0) return 0;
+        CC_REQUIRE(a.sum == m.sum && b.sum == m.sum, "contingency table sizes disagree (measures.py:115)");
+        const double np = (double)m.sum, lg = std::log2(np);
+        // entropies in bits: H = log2(N) - (1/N) sum c log2 c
+        const double h_ab = lg - m.clog / np, h_a = lg - a.clog / np, h_b = lg - b.clog / np;
+        out->vi_split = h_ab - h_a;     // H(seg | gt)
+        out->vi_merge = h_ab - h_b;     // H(gt | seg)
+        const double prec = m.sq / b.sq, rec = m.sq / a.sq;
+        out->adapted_rand_error = 1.0 - 2.0 * prec * rec / (prec + rec);
+        out->rand_index = 1.0 - (a.sq + b.sq - 2.0 * m.sq) / (np * np);
+        out->sum_sq_pairs = m.sq;
+        out->sum_sq_gt = a.sq;
+        out->sum_sq_seg = b.sq;
+        return 0;
     }
 }
 

@@ -242,41 +242,27 @@ static bool gr_pass(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], c
     CC_REQUIRE(nv < ((unsigned __int128)1 << 60), "region graph: volume too large");
     const GrGeom g = gr_geom(shape, owned, GR_R);
     const unsigned grid = gr_grid(g);
-    c->counter.ensure(3 * sizeof(u32));
-    int64_t cap = std::max<int64_t>(c->gr_cap, 1 << 16);
-    {
-        const int64_t want = 2 * std::min<int64_t>(std::min<int64_t>(hint, 4 * (int64_t)nv), 1LL << 27);
-        while (cap < want) cap *= 2;
-    }
-    for (;;) {
+    p.cap = table_pass(c->gr_cap, 1 << 16, std::min<int64_t>(hint, 4 * (int64_t)nv), "more than 2^30 nodes and edges", [&](int64_t cap) {
         c->gr_tab.ensure(2 * cap * sizeof(u64));      // keys | counts
         c->gr_comp.ensure(3 * cap * sizeof(u64));     // compacted nodes | edge keys | edge counts
         u64* keys = c->gr_tab.as<u64>();
         u64* cnts = keys + cap;
         u64* comp = c->gr_comp.as<u64>();
-        HIP_OK(hipMemsetAsync(keys, 0xFF, cap * sizeof(u64), s));
-        HIP_OK(hipMemsetAsync(cnts, 0, cap * sizeof(u64), s));
-        HIP_OK(hipMemsetAsync(c->counter.p, 0, 3 * sizeof(u32), s));
-        u32* err = c->counter.as<u32>();
+        table_clear(c, keys, cap * sizeof(u64), cap * sizeof(u64));
+        u32* err = counters_clear(c, 3);
         launch(c, "k_graph", [&] { k_graph<<<grid, GR_WG, 0, s>>>(labels, g, ignore_label ? 1 : 0, keys, cnts, (u64)cap - 1, err); });
         launch(c, "k_gr_compact", [&] {
             k_gr_compact<<<grid_stride(cap), 256, 0, s>>>(keys, cnts, (u64)cap, comp, comp + cap, comp + 2 * cap, err + 1);
         });
         u32 h[3] = {0, 0, 0};
-        HIP_OK(hipMemcpyAsync(h, c->counter.p, 3 * sizeof(u32), hipMemcpyDeviceToHost, s));
-        sync(c);
+        counters_read(c, h);
         CC_REQUIRE(!(h[0] & EV_ERR_GT), "label id 2^64 - 1 is reserved");
         if (h[0] & GR_ERR_RANGE) throw CCIdRangeError{{"label id >= 2^32 - 1 (region graph keys pack two ids in 64 bits)"}};
-        const int64_t nn = h[1], ne = h[2];
-        if ((h[0] & EV_ERR_FULL) || (nn + ne) * 2 > cap) {
-            CC_REQUIRE(cap < (1LL << 31), "more than 2^30 nodes and edges");
-            cap *= 4;
-            continue;
-        }
-        c->gr_cap = cap;
-        p.cap = cap; p.nn = nn; p.ne = ne;
-        return true;
-    }
+        p.nn = h[1];
+        p.ne = h[2];
+        return TableFill{(h[0] & EV_ERR_FULL) != 0, p.nn + p.ne};
+    });
+    return true;
 }
 
 static int region_graph_impl(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], const int64_t owned[3],

@@ -273,61 +273,49 @@ int cc_morphology(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], con
         const SfGeom g = sf_geom(labels, labels, n);
         const u32 X = (u32)shape[2], Y = (u32)shape[1];
         const u32 rX = X == 1 ? ~0u : (u32)((1ull << 32) / X), rY = Y == 1 ? ~0u : (u32)((1ull << 32) / Y);
-        c->counter.ensure(2 * sizeof(u32));
-        int64_t cap = std::max<int64_t>(c->mo_cap, 1 << 16);
-        if (rows_host && cap_host > 0) {
-            const int64_t want = 2 * std::min<int64_t>(std::min<int64_t>(cap_host, n), 1LL << 27);
-            while (cap < want) cap *= 2;
-        }
-        for (;;) {
+        MoTab t;
+        u64* comp = nullptr;
+        int64_t nu = 0;
+        const int64_t cap = table_pass(c->mo_cap, 1 << 16, rows_host ? std::min(cap_host, n) : 0, "more than 2^30 distinct ids",
+                                       [&](int64_t cap) {
             // keys (u64) | min bounds (3 u32) -- all ones; sums (4 u64) | max bounds (3 u32) -- zero
             c->mo_tab.ensure((size_t)cap * 64);
             c->sf_comp.ensure((size_t)cap * (sizeof(u64) + sizeof(u32)));     // compacted ids | slots
-            MoTab t;
             t.keys = c->mo_tab.as<u64>();
             t.lo = reinterpret_cast<u32*>(t.keys + cap);
             t.acc = reinterpret_cast<u64*>(t.lo + 3 * cap);
             t.hi = reinterpret_cast<u32*>(t.acc + 4 * cap);
             t.mask = (u64)cap - 1;
-            u64* comp = c->sf_comp.as<u64>();
-            u32* comp_slot = reinterpret_cast<u32*>(comp + cap);
-            HIP_OK(hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 20, s));
-            HIP_OK(hipMemsetAsync(t.acc, 0, (size_t)cap * 44, s));
-            HIP_OK(hipMemsetAsync(c->counter.p, 0, 2 * sizeof(u32), s));
-            u32* err = c->counter.as<u32>();
+            comp = c->sf_comp.as<u64>();
+            table_clear(c, t.keys, (size_t)cap * 20, (size_t)cap * 44);
+            u32* err = counters_clear(c, 2);
             launch(c, "k_morph", [&] {
                 if (g.vw2) k_morph<2><<<g.grid, RL_WG, 0, s>>>(labels, n, g.per_wg, X, Y, rX, rY, t, err);
                 else k_morph<1><<<g.grid, RL_WG, 0, s>>>(labels, n, g.per_wg, X, Y, rX, rY, t, err);
             });
             launch(c, "k_mo_compact", [&] {
-                k_mo_compact<<<grid_stride(cap), 256, 0, s>>>(t.keys, (u64)cap, comp, comp_slot, err + 1);
+                k_mo_compact<<<grid_stride(cap), 256, 0, s>>>(t.keys, (u64)cap, comp, reinterpret_cast<u32*>(comp + cap), err + 1);
             });
             u32 h[2] = {0, 0};
-            HIP_OK(hipMemcpyAsync(h, c->counter.p, 2 * sizeof(u32), hipMemcpyDeviceToHost, s));
-            sync(c);
+            counters_read(c, h);
             CC_REQUIRE(!(h[0] & EV_ERR_GT), "label id 2^64 - 1 is reserved");
-            if ((h[0] & EV_ERR_FULL) || (int64_t)h[1] * 2 > cap) {
-                CC_REQUIRE(cap < (1LL << 31), "more than 2^30 distinct ids");
-                cap *= 4;
-                continue;
-            }
-            const int64_t nu = h[1];
-            c->mo_cap = cap;
-            *n_unique = (uint64_t)nu;
-            if (!rows_host || cap_host < nu) return 0;
-            // sorted ids | rows (u64), then the sorted slots (u32)
-            c->mo_rows.ensure((size_t)(12 * nu + 1) * sizeof(u64) + (size_t)(nu + 1) * sizeof(u32));
-            u64* ids = c->mo_rows.as<u64>();
-            u64* rows = ids + nu;
-            u32* slot = reinterpret_cast<u32*>(rows + 11 * nu);
-            launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u32>(comp, ids, comp_slot, slot, nu, 0, 64, c->cub_tmp, s); });
-            launch(c, "k_mo_rows", [&] {
-                k_mo_rows<<<grid1d(nu), 256, 0, s>>>(ids, slot, nu, t, (u64)origin[0], (u64)origin[1], (u64)origin[2], rows);
-            });
-            HIP_OK(hipMemcpyAsync(rows_host, rows, (size_t)nu * 11 * sizeof(u64), hipMemcpyDeviceToHost, s));
-            sync(c);
-            return 0;
-        }
+            nu = h[1];
+            return TableFill{(h[0] & EV_ERR_FULL) != 0, nu};
+        });
+        *n_unique = (uint64_t)nu;
+        if (!rows_host || cap_host < nu) return 0;
+        u32* comp_slot = reinterpret_cast<u32*>(comp + cap);
+        // sorted ids | rows (u64), then the sorted slots (u32)
+        c->mo_rows.ensure((size_t)(12 * nu + 1) * sizeof(u64) + (size_t)(nu + 1) * sizeof(u32));
+        u64* ids = c->mo_rows.as<u64>();
+        u64* rows = ids + nu;
+        u32* slot = reinterpret_cast<u32*>(rows + 11 * nu);
+        launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u32>(comp, ids, comp_slot, slot, nu, 0, 64, c->cub_tmp, s); });
+        launch(c, "k_mo_rows", [&] {
+            k_mo_rows<<<grid1d(nu), 256, 0, s>>>(ids, slot, nu, t, (u64)origin[0], (u64)origin[1], (u64)origin[2], rows);
+        });
+        HIP_OK(hipMemcpyAsync(rows_host, rows, (size_t)nu * 11 * sizeof(u64), hipMemcpyDeviceToHost, s));
+        sync(c);
     })
 }
 

@@ -22,7 +22,7 @@
 // (ws, label) keys across the 64 lanes by one ballot, run heads add (key, length) to the
 // workgroup's LDS table, flushed once to the HBM open-addressing tables; pairs of a ws-0 voxel
 // wait per block (ZTAG keys) for k_ev_fold, which adds those of the blocks that held a non-zero
-// ws voxel.  The occupied slots are compacted on the device (k_nl_compact), sorted by key --
+// ws voxel.  The occupied slots are compacted on the device (k_tab_compact), sorted by key --
 // (ws id, label id) order -- and unpacked into three arrays that stay in the context for
 // cc_max_overlaps.
 //
@@ -142,18 +142,6 @@ __global__ __launch_bounds__(256) void k_nl_overlaps(const u64* __restrict__ ws,
         if (lk[e] != EV_EMPTY) ev_global(t, lk[e], lc[e]);
 }
 
-// the occupied slots of the pair table, in any order (the sort follows); *count = their number
-__global__ __launch_bounds__(256) void k_nl_compact(const u64* __restrict__ keys, const u64* __restrict__ cnts, u64 cap,
-                                                    u64* out_keys, u64* out_cnts, u32* count) {
-    for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < cap; e += (u64)gridDim.x * 256) {
-        const u64 k = keys[e];
-        if (k == EV_EMPTY) continue;
-        const u32 at = atomicAdd(count, 1u);
-        out_keys[at] = k;
-        out_cnts[at] = cnts[e];
-    }
-}
-
 // sorted keys -> (ws id, label id)
 __global__ __launch_bounds__(256) void k_nl_unpack(const u64* __restrict__ keys, int64_t n, u64* ws_ids, u64* label_ids) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -225,25 +213,18 @@ static int label_overlaps_impl(cc_ctx* c, const uint64_t* ws, const void* labels
     const int64_t rows_per_wg = std::max<int64_t>(1, (n_rows + 8191) / 8192);
     const unsigned grid = (unsigned)((n_rows + rows_per_wg - 1) / rows_per_wg);
     c->nl_flag.ensure(n_blocks * sizeof(u32) + 16);
-    c->counter.ensure(2 * sizeof(u32));
-    int64_t cap = std::max<int64_t>(c->nl_cap, 1 << 16);
-    {
-        const int64_t hint = 2 * std::min<int64_t>(host_cap, 1LL << 27);
-        while (cap < hint) cap *= 2;
-    }
-    for (;;) {
+    int64_t n = 0;
+    u64* comp = nullptr;
+    // keep the table at most half full (linear probing); grow and rerun otherwise
+    const int64_t cap = table_pass(c->nl_cap, 1 << 16, host_cap, "overlap table larger than 2^30 pairs", [&](int64_t cap) {
         c->nl_tab.ensure(4 * cap * sizeof(u64));       // pair keys | counts | ws-0 keys | counts
         c->nl_comp.ensure(2 * cap * sizeof(u64));      // compacted keys | counts
         u64* mk = c->nl_tab.as<u64>();
         u64* zk = mk + 2 * cap;
-        u64* comp = c->nl_comp.as<u64>();
-        for (u64* k : {mk, zk}) {
-            HIP_OK(hipMemsetAsync(k, 0xFF, cap * sizeof(u64), s));
-            HIP_OK(hipMemsetAsync(k + cap, 0, cap * sizeof(u64), s));
-        }
+        comp = c->nl_comp.as<u64>();
+        for (u64* k : {mk, zk}) table_clear(c, k, cap * sizeof(u64), cap * sizeof(u64));
         HIP_OK(hipMemsetAsync(c->nl_flag.p, 0, n_blocks * sizeof(u32), s));
-        HIP_OK(hipMemsetAsync(c->counter.p, 0, 2 * sizeof(u32), s));
-        u32* err = c->counter.as<u32>();
+        u32* err = counters_clear(c, 2);
         EvTabs t{mk, mk + cap, zk, zk + cap, (u64)cap - 1, err};
         u32* flag = c->nl_flag.as<u32>();
         const int ui = use_ignore ? 1 : 0;
@@ -254,40 +235,34 @@ static int label_overlaps_impl(cc_ctx* c, const uint64_t* ws, const void* labels
             default: nl_launch<u64>(c, grid, ws, labels, n_rows, rows_per_wg, gr, ui, ignore_label, t, flag); break;
         }
         launch(c, "k_ev_fold", [&] { k_ev_fold<<<grid_stride(cap), 256, 0, s>>>(t, flag); });
-        launch(c, "k_nl_compact", [&] { k_nl_compact<<<grid_stride(cap), 256, 0, s>>>(mk, mk + cap, (u64)cap, comp, comp + cap, err + 1); });
+        // (the kernel is k_tab_compact; the profile keeps this pass's own name for it)
+        launch(c, "k_nl_compact", [&] { k_tab_compact<<<grid_stride(cap), 256, 0, s>>>(mk, mk + cap, (u64)cap, comp, comp + cap, err + 1); });
         u32 h[2] = {0, 0};
-        HIP_OK(hipMemcpyAsync(h, c->counter.p, 2 * sizeof(u32), hipMemcpyDeviceToHost, s));
-        sync(c);
+        counters_read(c, h);
         if (h[0] & EV_ERR_SEG) throw CCIdRangeError{{"ws id >= 2^31 (overlap keys pack ws ids in 31 bits)"}};
         if (h[0] & EV_ERR_GT) throw CCIdRangeError{{"label id >= 2^32 - 1 (overlap keys pack label ids in 32 bits)"}};
-        const int64_t n = h[1];
-        // keep the table at most half full (linear probing); grow and rerun otherwise
-        if ((h[0] & EV_ERR_FULL) || n * 2 > cap) {
-            CC_REQUIRE(cap < (1LL << 31), "overlap table larger than 2^30 pairs");
-            cap *= 4;
-            continue;
-        }
-        c->nl_cap = cap;
-        // sorted keys | ws ids | label ids | counts: the triples stay here for cc_max_overlaps
-        c->nl_sorted.ensure((size_t)(4 * n + 4) * sizeof(u64));
-        u64* skey = c->nl_sorted.as<u64>();
-        u64* wid = skey + n + 1;
-        u64* lid = wid + n + 1;
-        u64* cnt = lid + n + 1;
-        if (n) {
-            launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp, skey, comp + cap, cnt, n, 0, 64, c->cub_tmp, s); });
-            launch(c, "k_nl_unpack", [&] { k_nl_unpack<<<grid1d(n), 256, 0, s>>>(skey, n, wid, lid); });
-        }
-        c->nl_n = n;
-        *n_out = (uint64_t)n;
-        if (want && n && n <= host_cap) {
-            HIP_OK(hipMemcpyAsync(ws_ids_host, wid, n * sizeof(u64), hipMemcpyDeviceToHost, s));
-            HIP_OK(hipMemcpyAsync(label_ids_host, lid, n * sizeof(u64), hipMemcpyDeviceToHost, s));
-            HIP_OK(hipMemcpyAsync(counts_host, cnt, n * sizeof(u64), hipMemcpyDeviceToHost, s));
-        }
-        sync(c);
-        return 0;
+        n = h[1];
+        return TableFill{(h[0] & EV_ERR_FULL) != 0, n};
+    });
+    // sorted keys | ws ids | label ids | counts: the triples stay here for cc_max_overlaps
+    c->nl_sorted.ensure((size_t)(4 * n + 4) * sizeof(u64));
+    u64* skey = c->nl_sorted.as<u64>();
+    u64* wid = skey + n + 1;
+    u64* lid = wid + n + 1;
+    u64* cnt = lid + n + 1;
+    if (n) {
+        launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp, skey, comp + cap, cnt, n, 0, 64, c->cub_tmp, s); });
+        launch(c, "k_nl_unpack", [&] { k_nl_unpack<<<grid1d(n), 256, 0, s>>>(skey, n, wid, lid); });
     }
+    c->nl_n = n;
+    *n_out = (uint64_t)n;
+    if (want && n && n <= host_cap) {
+        HIP_OK(hipMemcpyAsync(ws_ids_host, wid, n * sizeof(u64), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(label_ids_host, lid, n * sizeof(u64), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(counts_host, cnt, n * sizeof(u64), hipMemcpyDeviceToHost, s));
+    }
+    sync(c);
+    return 0;
 }
 
 static void max_overlaps_impl(cc_ctx* c, const uint64_t* ws_ids, const uint64_t* label_ids, const uint64_t* counts, int64_t n,

@@ -311,29 +311,23 @@ int cc_region_features(cc_ctx* c, const uint64_t* labels, const void* values, in
         // two ids per lane need 16-B labels and one aligned load of the lane's two values
         const bool pair_ok = (uintptr_t)values % (f32 ? 8 : 2) == 0;
         const SfGeom g = sf_geom(labels, pair_ok ? labels : labels + 1, n);
-        c->counter.ensure(2 * sizeof(u32));
-        int64_t cap = std::max<int64_t>(c->rf_cap, 1 << 16);
-        if (host_tab && cap_host > 0) {
-            const int64_t want = 2 * std::min<int64_t>(std::min<int64_t>(cap_host, n), 1LL << 27);
-            while (cap < want) cap *= 2;
-        }
-        for (;;) {
+        RfTab t;
+        u64* comp = nullptr;
+        int64_t nu = 0;
+        const int64_t cap = table_pass(c->rf_cap, 1 << 16, host_tab ? std::min(cap_host, n) : 0, "more than 2^30 distinct ids",
+                                       [&](int64_t cap) {
             // keys (u64) | minimum keys (u32) -- all ones; counts | sums (u64) | maximum keys (u32) -- zero
             c->rf_tab.ensure((size_t)cap * 32);
             c->sf_comp.ensure((size_t)cap * (sizeof(u64) + sizeof(u32)));     // compacted ids | slots
-            RfTab t;
             t.keys = c->rf_tab.as<u64>();
             t.kmn = reinterpret_cast<u32*>(t.keys + cap);
             t.cnt = reinterpret_cast<u64*>(t.kmn + cap);
             t.sum = t.cnt + cap;
             t.kmx = reinterpret_cast<u32*>(t.sum + cap);
             t.mask = (u64)cap - 1;
-            u64* comp = c->sf_comp.as<u64>();
-            u32* comp_slot = reinterpret_cast<u32*>(comp + cap);
-            HIP_OK(hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 12, s));
-            HIP_OK(hipMemsetAsync(t.cnt, 0, (size_t)cap * 20, s));
-            HIP_OK(hipMemsetAsync(c->counter.p, 0, 2 * sizeof(u32), s));
-            u32* err = c->counter.as<u32>();
+            comp = c->sf_comp.as<u64>();
+            table_clear(c, t.keys, (size_t)cap * 12, (size_t)cap * 20);
+            u32* err = counters_clear(c, 2);
             launch(c, "k_rf", [&] {
                 const float* vf = static_cast<const float*>(values);
                 const unsigned char* vb = static_cast<const unsigned char*>(values);
@@ -343,42 +337,36 @@ int cc_region_features(cc_ctx* c, const uint64_t* labels, const void* values, in
                 else k_rf<1, unsigned char><<<g.grid, RL_WG, 0, s>>>(labels, vb, n, g.per_wg, t, err);
             });
             launch(c, "k_mo_compact", [&] {
-                k_mo_compact<<<grid_stride(cap), 256, 0, s>>>(t.keys, (u64)cap, comp, comp_slot, err + 1);
+                k_mo_compact<<<grid_stride(cap), 256, 0, s>>>(t.keys, (u64)cap, comp, reinterpret_cast<u32*>(comp + cap), err + 1);
             });
             u32 h[2] = {0, 0};
-            HIP_OK(hipMemcpyAsync(h, c->counter.p, 2 * sizeof(u32), hipMemcpyDeviceToHost, s));
-            sync(c);
+            counters_read(c, h);
             CC_REQUIRE(!(h[0] & EV_ERR_GT), "label id 2^64 - 1 is reserved");
-            if ((h[0] & EV_ERR_FULL) || (int64_t)h[1] * 2 > cap) {
-                CC_REQUIRE(cap < (1LL << 31), "more than 2^30 distinct ids");
-                cap *= 4;
-                continue;
-            }
-            const int64_t nu = h[1];
-            c->rf_cap = cap;
-            *n_unique = (uint64_t)nu;
-            if (!host_tab || cap_host < nu) return 0;
-            // sorted ids | counts | sums (8 B each), then minima | maxima (float) | sorted slots (u32)
-            c->rf_rows.ensure((size_t)(3 * nu + 3) * sizeof(u64) + (size_t)(3 * nu + 3) * sizeof(u32));
-            u64* ids = c->rf_rows.as<u64>();
-            u64* counts = ids + nu + 1;
-            double* sums = reinterpret_cast<double*>(counts + nu + 1);
-            float* mins = reinterpret_cast<float*>(sums + nu + 1);
-            float* maxs = mins + nu + 1;
-            u32* slot = reinterpret_cast<u32*>(maxs + nu + 1);
-            launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u32>(comp, ids, comp_slot, slot, nu, 0, 64, c->cub_tmp, s); });
-            launch(c, "k_rf_rows", [&] {
-                if (f32) k_rf_rows<float><<<grid1d(nu), 256, 0, s>>>(slot, nu, t, counts, sums, mins, maxs);
-                else k_rf_rows<unsigned char><<<grid1d(nu), 256, 0, s>>>(slot, nu, t, counts, sums, mins, maxs);
-            });
-            if (ids_host) HIP_OK(hipMemcpyAsync(ids_host, ids, (size_t)nu * sizeof(u64), hipMemcpyDeviceToHost, s));
-            if (counts_host) HIP_OK(hipMemcpyAsync(counts_host, counts, (size_t)nu * sizeof(u64), hipMemcpyDeviceToHost, s));
-            if (sums_host) HIP_OK(hipMemcpyAsync(sums_host, sums, (size_t)nu * sizeof(double), hipMemcpyDeviceToHost, s));
-            if (mins_host) HIP_OK(hipMemcpyAsync(mins_host, mins, (size_t)nu * sizeof(float), hipMemcpyDeviceToHost, s));
-            if (maxs_host) HIP_OK(hipMemcpyAsync(maxs_host, maxs, (size_t)nu * sizeof(float), hipMemcpyDeviceToHost, s));
-            sync(c);
-            return 0;
-        }
+            nu = h[1];
+            return TableFill{(h[0] & EV_ERR_FULL) != 0, nu};
+        });
+        *n_unique = (uint64_t)nu;
+        if (!host_tab || cap_host < nu) return 0;
+        u32* comp_slot = reinterpret_cast<u32*>(comp + cap);
+        // sorted ids | counts | sums (8 B each), then minima | maxima (float) | sorted slots (u32)
+        c->rf_rows.ensure((size_t)(3 * nu + 3) * sizeof(u64) + (size_t)(3 * nu + 3) * sizeof(u32));
+        u64* ids = c->rf_rows.as<u64>();
+        u64* counts = ids + nu + 1;
+        double* sums = reinterpret_cast<double*>(counts + nu + 1);
+        float* mins = reinterpret_cast<float*>(sums + nu + 1);
+        float* maxs = mins + nu + 1;
+        u32* slot = reinterpret_cast<u32*>(maxs + nu + 1);
+        launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u32>(comp, ids, comp_slot, slot, nu, 0, 64, c->cub_tmp, s); });
+        launch(c, "k_rf_rows", [&] {
+            if (f32) k_rf_rows<float><<<grid1d(nu), 256, 0, s>>>(slot, nu, t, counts, sums, mins, maxs);
+            else k_rf_rows<unsigned char><<<grid1d(nu), 256, 0, s>>>(slot, nu, t, counts, sums, mins, maxs);
+        });
+        if (ids_host) HIP_OK(hipMemcpyAsync(ids_host, ids, (size_t)nu * sizeof(u64), hipMemcpyDeviceToHost, s));
+        if (counts_host) HIP_OK(hipMemcpyAsync(counts_host, counts, (size_t)nu * sizeof(u64), hipMemcpyDeviceToHost, s));
+        if (sums_host) HIP_OK(hipMemcpyAsync(sums_host, sums, (size_t)nu * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (mins_host) HIP_OK(hipMemcpyAsync(mins_host, mins, (size_t)nu * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (maxs_host) HIP_OK(hipMemcpyAsync(maxs_host, maxs, (size_t)nu * sizeof(float), hipMemcpyDeviceToHost, s));
+        sync(c);
     })
 }
 

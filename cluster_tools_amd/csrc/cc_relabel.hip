@@ -285,65 +285,52 @@ int cc_relabel_consecutive(cc_ctx* c, const uint64_t* labels, uint64_t* out, int
         c->rl_wg.ensure((size_t)ugrid * (EV_LDS * sizeof(u64) + sizeof(u32)));
         u64* WGL = c->rl_wg.as<u64>();
         u32* WGN = reinterpret_cast<u32*>(WGL + (size_t)ugrid * EV_LDS);
-        c->counter.ensure(2 * sizeof(u32));
-        // id-set slots: at least twice the caller's table capacity (its expected number of distinct
-        // ids, bounded by n), so the set is sized right on the first pass -- a set that fills up
-        // makes every further insert walk EV_PROBES slots before the pass is rerun larger (the
-        // 666 ms first call of round 2); grown sets are kept for the next call
-        int64_t cap = std::max<int64_t>(c->rl_cap, 1 << 16);
-        if (uniques_host && cap_host > 0) {
-            const int64_t want = 2 * std::min<int64_t>(std::min<int64_t>(cap_host, n), 1LL << 27);
-            while (cap < want) cap *= 2;
-        }
-        for (;;) {
+        // id-set slots: the caller's table capacity is its expected number of distinct ids (bounded
+        // by n), so the set is sized right on the first pass (the 666 ms first call of round 2)
+        u64 *keys = nullptr, *comp = nullptr;
+        int64_t nu = 0;
+        const int64_t cap = table_pass(c->rl_cap, 1 << 16, uniques_host ? std::min(cap_host, n) : 0, "more than 2^30 distinct ids",
+                                       [&](int64_t cap) {
             c->ev_seg.ensure(2 * cap * sizeof(u64));     // keys | new ids
-            u64* keys = c->ev_seg.as<u64>();
-            u64* vals = keys + cap;
+            keys = c->ev_seg.as<u64>();
             HIP_OK(hipMemsetAsync(keys, 0xFF, cap * sizeof(u64), s));
-            HIP_OK(hipMemsetAsync(c->counter.p, 0, 2 * sizeof(u32), s));
-            u32* err = c->counter.as<u32>();
+            u32* err = counters_clear(c, 2);
             launch(c, "k_rl_unique", [&] {
                 if (vw2) k_rl_unique<2><<<ugrid, RL_WG, 0, s>>>(labels, n, per_wg, keys, (u64)cap - 1, err, WGL, WGN);
                 else k_rl_unique<1><<<ugrid, RL_WG, 0, s>>>(labels, n, per_wg, keys, (u64)cap - 1, err, WGL, WGN);
             });
-            u32 h[2] = {0, 0};
             c->ev_gt.ensure(cap * 2 * sizeof(u64));      // compacted ids | sorted ids
-            u64* comp = c->ev_gt.as<u64>();
-            u64* sorted = comp + cap;
+            comp = c->ev_gt.as<u64>();
             launch(c, "k_rl_compact", [&] { k_rl_compact<<<grid_stride(cap), 256, 0, s>>>(keys, (u64)cap, comp, err + 1); });
-            HIP_OK(hipMemcpyAsync(h, c->counter.p, 2 * sizeof(u32), hipMemcpyDeviceToHost, s));
-            sync(c);
+            u32 h[2] = {0, 0};
+            counters_read(c, h);
             CC_REQUIRE(!(h[0] & EV_ERR_GT), "label id 2^64 - 1 is reserved");
-            if ((h[0] & EV_ERR_FULL) || (int64_t)h[1] * 2 > cap) {
-                CC_REQUIRE(cap < (1LL << 31), "more than 2^30 distinct ids");
-                cap *= 4;
-                continue;
-            }
-            const int64_t nu = h[1];
-            launch(c, "radix_sort", [&] { prims::sort_keys<u64>(comp, sorted, nu, 0, 64, c->cub_tmp, s); });
-            u64 first = 1;
-            HIP_OK(hipMemcpyAsync(&first, sorted, sizeof(u64), hipMemcpyDeviceToHost, s));
-            sync(c);
-            const u64 start = first == 0 ? 0 : 1;
-            c->rl_cap = cap;
-            *n_unique = (uint64_t)nu;
-            *start_label = start;
-            // the table does not fit the caller's buffer: report its size and leave out_dev
-            // untouched (an in-place call must not lose the ids before the table is returned)
-            if (uniques_host && cap_host < nu) return 0;
-            launch(c, "k_rl_assign", [&] {
-                k_rl_assign<<<grid1d(nu), 256, 0, s>>>(sorted, nu, start, keys, (u64)cap - 1, vals);
-            });
-            launch(c, "k_rl_apply", [&] {
-                if (vw2) k_rl_apply<2><<<ugrid, RL_WG, 0, s>>>(labels, n, per_wg, keys, (u64)cap - 1, vals, WGL, WGN, out);
-                else k_rl_apply<1><<<ugrid, RL_WG, 0, s>>>(labels, n, per_wg, keys, (u64)cap - 1, vals, WGL, WGN, out);
-            });
-            if (uniques_host && cap_host > 0)
-                HIP_OK(hipMemcpyAsync(uniques_host, sorted, std::min<int64_t>(cap_host, nu) * sizeof(u64),
-                                      hipMemcpyDeviceToHost, s));
-            sync(c);
-            return 0;
-        }
+            nu = h[1];
+            return TableFill{(h[0] & EV_ERR_FULL) != 0, nu};
+        });
+        u64* vals = keys + cap;
+        u64* sorted = comp + cap;
+        launch(c, "radix_sort", [&] { prims::sort_keys<u64>(comp, sorted, nu, 0, 64, c->cub_tmp, s); });
+        u64 first = 1;
+        HIP_OK(hipMemcpyAsync(&first, sorted, sizeof(u64), hipMemcpyDeviceToHost, s));
+        sync(c);
+        const u64 start = first == 0 ? 0 : 1;
+        *n_unique = (uint64_t)nu;
+        *start_label = start;
+        // the table does not fit the caller's buffer: report its size and leave out_dev
+        // untouched (an in-place call must not lose the ids before the table is returned)
+        if (uniques_host && cap_host < nu) return 0;
+        launch(c, "k_rl_assign", [&] {
+            k_rl_assign<<<grid1d(nu), 256, 0, s>>>(sorted, nu, start, keys, (u64)cap - 1, vals);
+        });
+        launch(c, "k_rl_apply", [&] {
+            if (vw2) k_rl_apply<2><<<ugrid, RL_WG, 0, s>>>(labels, n, per_wg, keys, (u64)cap - 1, vals, WGL, WGN, out);
+            else k_rl_apply<1><<<ugrid, RL_WG, 0, s>>>(labels, n, per_wg, keys, (u64)cap - 1, vals, WGL, WGN, out);
+        });
+        if (uniques_host && cap_host > 0)
+            HIP_OK(hipMemcpyAsync(uniques_host, sorted, std::min<int64_t>(cap_host, nu) * sizeof(u64),
+                                  hipMemcpyDeviceToHost, s));
+        sync(c);
     })
 }
 

@@ -146,17 +146,6 @@ __global__ __launch_bounds__(RL_WG) void k_sf_count(const u64* __restrict__ lab,
     if (threadIdx.x == 0) WGN[blockIdx.x] = keep_list ? ln : ~0u;
 }
 
-__global__ __launch_bounds__(256) void k_sf_compact(const u64* __restrict__ keys, const u64* __restrict__ cnts, u64 cap,
-                                                    u64* out_ids, u64* out_cnt, u32* count) {
-    for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < cap; e += (u64)gridDim.x * 256) {
-        const u64 k = keys[e];
-        if (k == EV_EMPTY) continue;
-        const u32 at = atomicAdd(count, 1u);
-        out_ids[at] = k;
-        out_cnt[at] = cnts[e];
-    }
-}
-
 // keep flags of the sorted ids; keep[nu] = 0 closes the scan
 // size_threshold: count >= t stays (size_filter_blocks.py:112: strict <)
 __global__ __launch_bounds__(256) void k_sf_mark_threshold(const u64* __restrict__ counts, int64_t nu, u64 t, u32* keep) {
@@ -259,65 +248,50 @@ struct SfTable {
     u32* WGN = nullptr;
 };
 
-// count pass with table growth and retry (as cc_relabel_consecutive), compaction and the sort
-// by id.  cap_hint: the expected number of distinct ids.
+// count pass (a table pass: cc_table_pass.hpp), compaction and the sort by id.  cap_hint: the
+// expected number of distinct ids.
 static SfTable sf_count(cc_ctx* c, const u64* labels, int64_t n, const SfGeom& g, int64_t cap_hint) {
     hipStream_t s = cstream(c);
     SfTable t;
     c->rl_wg.ensure((size_t)g.grid * (EV_LDS * sizeof(u64) + sizeof(u32)));
     t.WGL = c->rl_wg.as<u64>();
     t.WGN = reinterpret_cast<u32*>(t.WGL + (size_t)g.grid * EV_LDS);
-    c->counter.ensure(2 * sizeof(u32));
-    int64_t cap = std::max<int64_t>(c->sf_cap, 1 << 16);
-    if (cap_hint > 0) {
-        const int64_t want = 2 * std::min<int64_t>(std::min<int64_t>(cap_hint, n), 1LL << 27);
-        while (cap < want) cap *= 2;
-    }
-    for (;;) {
+    u64* comp = nullptr;
+    t.cap = table_pass(c->sf_cap, 1 << 16, std::min(cap_hint, n), "more than 2^30 distinct ids", [&](int64_t cap) {
         c->sf_tab.ensure(2 * cap * sizeof(u64));      // keys | counts
         c->sf_comp.ensure(2 * cap * sizeof(u64));     // compacted ids | counts
-        u64* keys = c->sf_tab.as<u64>();
-        u64* cnts = keys + cap;
-        u64* comp = c->sf_comp.as<u64>();
-        HIP_OK(hipMemsetAsync(keys, 0xFF, cap * sizeof(u64), s));
-        HIP_OK(hipMemsetAsync(cnts, 0, cap * sizeof(u64), s));
-        HIP_OK(hipMemsetAsync(c->counter.p, 0, 2 * sizeof(u32), s));
-        u32* err = c->counter.as<u32>();
+        t.keys = c->sf_tab.as<u64>();
+        t.vals = t.keys + cap;
+        comp = c->sf_comp.as<u64>();
+        table_clear(c, t.keys, cap * sizeof(u64), cap * sizeof(u64));
+        u32* err = counters_clear(c, 2);
         launch(c, "k_sf_count", [&] {
-            if (g.vw2) k_sf_count<2><<<g.grid, RL_WG, 0, s>>>(labels, n, g.per_wg, keys, cnts, (u64)cap - 1, err, t.WGL, t.WGN);
-            else k_sf_count<1><<<g.grid, RL_WG, 0, s>>>(labels, n, g.per_wg, keys, cnts, (u64)cap - 1, err, t.WGL, t.WGN);
+            if (g.vw2) k_sf_count<2><<<g.grid, RL_WG, 0, s>>>(labels, n, g.per_wg, t.keys, t.vals, (u64)cap - 1, err, t.WGL, t.WGN);
+            else k_sf_count<1><<<g.grid, RL_WG, 0, s>>>(labels, n, g.per_wg, t.keys, t.vals, (u64)cap - 1, err, t.WGL, t.WGN);
         });
+        // (the kernel is k_tab_compact; the profile keeps this pass's own name for it)
         launch(c, "k_sf_compact", [&] {
-            k_sf_compact<<<grid_stride(cap), 256, 0, s>>>(keys, cnts, (u64)cap, comp, comp + cap, err + 1);
+            k_tab_compact<<<grid_stride(cap), 256, 0, s>>>(t.keys, t.vals, (u64)cap, comp, comp + cap, err + 1);
         });
         u32 h[2] = {0, 0};
-        HIP_OK(hipMemcpyAsync(h, c->counter.p, 2 * sizeof(u32), hipMemcpyDeviceToHost, s));
-        sync(c);
+        counters_read(c, h);
         CC_REQUIRE(!(h[0] & EV_ERR_GT), "label id 2^64 - 1 is reserved");
-        if ((h[0] & EV_ERR_FULL) || (int64_t)h[1] * 2 > cap) {
-            CC_REQUIRE(cap < (1LL << 31), "more than 2^30 distinct ids");
-            cap *= 4;
-            continue;
-        }
-        const int64_t nu = h[1];
-        c->sf_cap = cap;
-        // ids | counts | new ids | sort scratch (u64), then keep | pos (nu + 1) | idx | order (u32)
-        c->sf_sorted.ensure((size_t)(4 * nu + 4) * sizeof(u64) + (size_t)(4 * nu + 8) * sizeof(u32));
-        t.nu = nu;
-        t.cap = cap;
-        t.keys = keys;
-        t.vals = cnts;
-        t.ids = c->sf_sorted.as<u64>();
-        t.counts = t.ids + nu + 1;
-        t.new_ids = t.counts + nu + 1;
-        t.skey = t.new_ids + nu + 1;
-        t.keep = reinterpret_cast<u32*>(t.skey + nu + 1);
-        t.pos = t.keep + nu + 2;
-        t.idx = t.pos + nu + 2;
-        t.order = t.idx + nu + 2;
-        launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp, t.ids, comp + cap, t.counts, nu, 0, 64, c->cub_tmp, s); });
-        return t;
-    }
+        t.nu = h[1];
+        return TableFill{(h[0] & EV_ERR_FULL) != 0, t.nu};
+    });
+    const int64_t nu = t.nu, cap = t.cap;
+    // ids | counts | new ids | sort scratch (u64), then keep | pos (nu + 1) | idx | order (u32)
+    c->sf_sorted.ensure((size_t)(4 * nu + 4) * sizeof(u64) + (size_t)(4 * nu + 8) * sizeof(u32));
+    t.ids = c->sf_sorted.as<u64>();
+    t.counts = t.ids + nu + 1;
+    t.new_ids = t.counts + nu + 1;
+    t.skey = t.new_ids + nu + 1;
+    t.keep = reinterpret_cast<u32*>(t.skey + nu + 1);
+    t.pos = t.keep + nu + 2;
+    t.idx = t.pos + nu + 2;
+    t.order = t.idx + nu + 2;
+    launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp, t.ids, comp + cap, t.counts, nu, 0, 64, c->cub_tmp, s); });
+    return t;
 }
 
 extern "C" {

@@ -147,6 +147,31 @@ def test_gpu_evaluate_table_growth(ctx):
 
 
 @pytest.mark.gpu
+def test_gpu_evaluate_table_growth_launches():
+    """fresh context, every voxel its own pair: 589 824 pairs, more than half of the 2^20 first
+    slots, so the tables are grown once and k_ev_overlaps runs twice"""
+    import torch
+    from cluster_tools_amd import _lib
+    from test_gpu_size_filter import table_launches
+    shape, bs = (64, 96, 96), (32, 48, 48)
+    n = int(np.prod(shape))
+    assert n == 589824 and 2 * n > 1 << 20
+    seg = (np.arange(n, dtype=np.uint64) + 1).reshape(shape)
+    gt = (np.random.default_rng(8).permutation(n).astype(np.uint64) + 1).reshape(shape)
+    want, ov = E.measures(seg, gt, bs, ignore_label=0)
+    with _lib.Context(0) as fresh:
+        fresh.set_profiling(1)
+        got = fresh.evaluate(torch.from_numpy(seg.view(np.int64)).cuda(),
+                             torch.from_numpy(gt.view(np.int64)).cuda(), bs)
+        assert got['n_pairs'] == want['n_pairs'] == len(ov) == n
+        for k in ('n_points', 'n_seg_ids', 'n_gt_ids'):
+            assert got[k] == want[k] == n, k
+        for k in ('vi_split', 'vi_merge', 'adapted_rand_error', 'rand_index'):
+            assert got[k] == pytest.approx(want[k], rel=RTOL, abs=1e-12), k
+        assert fresh.profile()['k_ev_overlaps']['count'] == table_launches(n, [0], first=1 << 20) == 2
+
+
+@pytest.mark.gpu
 def test_gpu_evaluate_cc_labels_at_scale(ctx):
     """Property at volume scale: the CCL output against a permuted relabelling of itself is the
     same partition (VI 0, RI 1, ARE 0); against the 'less' labelling with ignore label 0 the

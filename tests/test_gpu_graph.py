@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import _graph_ref as GR
-from test_gpu_size_filter import _dev, _host
+from test_gpu_size_filter import _dev, _host, table_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -75,16 +75,20 @@ def test_gpu_graph_checkerboard_two_ids(ctx):
 def test_gpu_graph_distinct_ids_table_growth():
     """every voxel its own id (39 780 ids, 114 484 edges of size 1): the workgroups' LDS tables
     are crowded (adds go straight to HBM), and with cap_hint=1 on a fresh context the HBM table
-    starts at 2^16 slots, fills up and is grown twice, the pass running again each time"""
+    starts at 2^16 slots, fills up and is grown twice, the pass running again each time; the host
+    arrays are too small and a second C call follows"""
     from cluster_tools_amd import _lib
     shape = (17, 18, 130)
     lab = (np.arange(int(np.prod(shape)), dtype=np.uint64) + 1).reshape(shape)
     with _lib.Context(0) as fresh:
+        fresh.set_profiling(1)
         got = check(fresh, lab, cap_hint=1)
         n = int(np.prod(shape))
         assert len(got['nodes']) == n == 39780
         assert len(got['edges']) == sum(n // s * (s - 1) for s in shape) == 114484
         assert (got['sizes'] == 1).all()
+        # the table's entries are the nodes and the edges; the first call expects 1 + 1 of them
+        assert fresh.profile()['k_graph']['count'] == table_launches(n + 114484, [2, n + 114484])
         check(fresh, lab, ignore_label=False, cap_hint=1)
 
 

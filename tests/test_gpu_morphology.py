@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import _morphology_ref as MR
-from test_gpu_size_filter import _dev, _host
+from test_gpu_size_filter import _dev, _host, grown_case, table_launches
 from test_size_filter_golden import sf_case
 
 pytestmark = pytest.mark.gpu
@@ -108,6 +108,19 @@ def test_gpu_morphology_all_distinct(ctx):
     lab = ((rng.permutation(n).astype(np.uint64) * np.uint64(4194301)) & np.uint64((1 << 40) - 1)).reshape(16, 128, 128)
     want = check(ctx, lab, cap_hint=1024)
     assert len(want) == n
+
+
+def test_gpu_morphology_table_growth_launches():
+    """fresh context, cap_hint=1, 65 600 ids: the table overflows its 2^16 first slots and grows on
+    the device, the host buffer is too small on the first C call of either Python call; k_morph
+    runs as often as the table-pass rule says"""
+    from cluster_tools_amd import _lib
+    lab = grown_case()
+    with _lib.Context(0) as fresh:
+        fresh.set_profiling(1)
+        want = check(fresh, lab, cap_hint=1)                   # raw rows, then the float table
+        assert len(want) == lab.size
+        assert fresh.profile()['k_morph']['count'] == table_launches(lab.size, [1, lab.size] * 2)
 
 
 def test_gpu_morphology_sparse_64bit_ids(ctx):

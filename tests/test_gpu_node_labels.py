@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import _node_labels_ref as NR
-from test_gpu_size_filter import _dev, _host
+from test_gpu_size_filter import _dev, _host, table_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -179,8 +179,11 @@ def test_gpu_node_labels_crowded_tables():
     ws = (np.arange(n, dtype=np.uint64) + 1).reshape(shape)
     lab = (np.arange(n, dtype=np.uint64)[::-1] * 3).reshape(shape)
     with _lib.Context(0) as fresh:
+        fresh.set_profiling(1)
         got = check(fresh, ws, lab, (2, 2, 1000), None, cap_hint=1)
         assert len(got['counts']) == n == 40800 and (got['counts'] == 1).all() and 2 * n > 1 << 16
+        # two C calls (the host arrays hold 1 triple, then n): the pass runs as the rule says
+        assert fresh.profile()['k_nl_overlaps']['count'] == table_launches(n, [1, n])
         got = check(fresh, ws, lab.astype(np.uint32), (2, 2, 1000), 0, cap_hint=1)
         assert len(got['counts']) == n - 1
 

@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 import _region_features_ref as RR
-from test_gpu_size_filter import _dev, _host
+from test_gpu_size_filter import _dev, _host, grown_case, table_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -154,6 +154,22 @@ def test_gpu_region_features_all_distinct(ctx, dtype):
     val = arbitrary(rng, n) if dtype == np.float32 else dyadic(rng, n, dtype)
     want = check(ctx, lab, val, cap_hint=1024)
     assert len(want['ids']) == n
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
+def test_gpu_region_features_table_growth_launches(dtype):
+    """fresh context, cap_hint=1, 65 600 ids: the table overflows its 2^16 first slots and grows on
+    the device, the host buffers are too small on the first C call of either Python call; k_rf
+    runs as often as the table-pass rule says"""
+    from cluster_tools_amd import _lib
+    lab = grown_case().reshape(-1)
+    rng = np.random.default_rng(13)
+    val = arbitrary(rng, lab.size) if dtype == np.float32 else dyadic(rng, lab.size, dtype)
+    with _lib.Context(0) as fresh:
+        fresh.set_profiling(1)
+        want = check(fresh, lab, val, cap_hint=1)              # raw table, then the float table
+        assert len(want['ids']) == lab.size
+        assert fresh.profile()['k_rf']['count'] == table_launches(lab.size, [1, lab.size] * 2)
 
 
 @pytest.mark.parametrize('dtype', DTYPES)

@@ -103,6 +103,47 @@ def test_gpu_size_filter_all_distinct(ctx):
     check(ctx, lab, cap_hint=1024, target_number=1000, relabels=(False,))
 
 
+def table_launches(entries, wants, first=1 << 16):
+    """Launches of a table pass's volume kernel over the C calls of a fresh context, by the rule of
+    the id-table passes: a call starts at max(kept, first) slots, doubled while below
+    2 min(want, 2^27) -- want: the entries that call's caller expects; a pass that leaves the table
+    more than half full (a full table is) runs again over four times the slots; the last capacity
+    is kept for the next call.  entries: the distinct entries of the volume."""
+    cap, launches = 0, 0
+    for want in wants:
+        cap = max(cap, first)
+        while cap < 2 * min(want, 1 << 27):
+            cap *= 2
+        launches += 1
+        while 2 * entries > cap:
+            cap *= 4
+            launches += 1
+    return launches
+
+
+def grown_case():
+    """40 x 40 x 41 voxels, every one its own id: 65 600 ids, more than the 2^16 first slots hold"""
+    shape = (40, 40, 41)
+    n = int(np.prod(shape))
+    lab = ((np.random.default_rng(12).permutation(n).astype(np.uint64) * np.uint64(4194301)) & np.uint64((1 << 40) - 1))
+    assert n == 65600 > 1 << 16 and len(np.unique(lab)) == n
+    return lab.reshape(shape)
+
+
+def test_gpu_size_filter_table_growth_launches():
+    """fresh context, cap_hint=1: the first C call's table overflows and is grown on the device,
+    the host buffers are too small and every Python call makes a second C call of the exact size;
+    the count pass runs as often as the rule says"""
+    from cluster_tools_amd import _lib
+    lab = grown_case()
+    n = lab.size
+    with _lib.Context(0) as fresh:
+        fresh.set_profiling(1)
+        # label_sizes, size_filter out of place and in place: three Python calls, two C calls each
+        check(fresh, lab, cap_hint=1, target_number=1000, relabels=(True,))
+        assert fresh.profile()['k_sf_count']['count'] == table_launches(n, [1, n] * 3)
+
+
 def test_gpu_size_filter_unaligned_odd(ctx):
     rng = np.random.default_rng(5)
     lab = np.repeat(rng.integers(0, 900, size=(9, 31, 29)), 3, axis=2).astype(np.uint64)

@@ -51,6 +51,26 @@ def test_gpu_relabel_matches_oracle(ctx, case):
 
 
 @pytest.mark.gpu
+def test_gpu_relabel_table_growth_launches():
+    """fresh context, cap_hint=1, 65 600 ids: the id set overflows its 2^16 first slots and grows
+    on the device, the host table is too small on the first C call; k_rl_unique runs as often as
+    the table-pass rule says"""
+    import torch
+    from cluster_tools_amd import _lib
+    from test_gpu_size_filter import grown_case, table_launches
+    lab = grown_case()
+    want, wa = R.relabel_consecutive(lab)
+    d = torch.from_numpy(lab.view(np.int64)).cuda()
+    with _lib.Context(0) as fresh:
+        fresh.set_profiling(1)
+        out, table = fresh.relabel_consecutive(d, cap_hint=1)
+        np.testing.assert_array_equal(d.cpu().numpy().view(np.uint64), lab)
+        np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64), want)
+        np.testing.assert_array_equal(table, wa)
+        assert fresh.profile()['k_rl_unique']['count'] == table_launches(lab.size, [1, lab.size])
+
+
+@pytest.mark.gpu
 def test_gpu_relabel_c3_scale(ctx):
     """C3 'less' labels: consecutive ids 1..n_components (0 kept), relabelling is idempotent,
     and the partition is unchanged (device contingency table is a bijection)."""
