@@ -52,6 +52,9 @@ class BaseClusterTask(Task):
     allow_retry = True
     n_retries = 0
 
+    def requires(self):
+        return self.dependency
+
     def run(self):
         self.make_dirs()
         self._write_log('Start task %s' % self.task_name)
@@ -134,6 +137,17 @@ class BaseClusterTask(Task):
 
     def output(self):
         return LocalTarget(os.path.join(self.tmp_folder, self.task_name + '.log'))
+
+    def prefixed_output(self, prefix):
+        """The target of a task that runs more than once per tmp folder: <tmp>/<task_name>_<prefix>.log"""
+        return LocalTarget(os.path.join(self.tmp_folder, '%s_%s.log' % (self.task_name, prefix)))
+
+    def run_jobs(self, n_jobs, block_list, config, job_prefix=None):
+        """Write the job configs, run the jobs and check their logs."""
+        self.prepare_jobs(n_jobs, block_list, config, job_prefix)
+        self.submit_jobs(n_jobs, job_prefix)
+        self.wait_for_jobs(job_prefix)
+        self.check_jobs(n_jobs, job_prefix)
 
     # ---- helpers ----
     def _write_log(self, msg):

@@ -13,12 +13,11 @@ input_path / overlap_key.
 import json
 import os
 
-import numpy as np
-
 from cluster_tools_amd.luigi_compat import Task, Parameter, TaskParameter, BoolParameter
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context, read_labels_u64, labels_to_device
 
 
 class MeasuresBase(Task):
@@ -34,9 +33,6 @@ class MeasuresBase(Task):
     ignore_label = BoolParameter(default=True)
     dependency = TaskParameter(default=DummyTask())
 
-    def requires(self):
-        return self.dependency
-
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end = self.global_config_values()
         self.init(shebang)
@@ -47,36 +43,19 @@ class MeasuresBase(Task):
         config.update({'seg_path': self.seg_path, 'seg_key': self.seg_key, 'gt_path': self.gt_path,
                        'gt_key': self.gt_key, 'output_path': self.output_path,
                        'ignore_label': 0 if self.ignore_label else None, 'block_shape': block_shape})
-        n_jobs = 1
-        self.prepare_jobs(n_jobs, None, config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(1, None, config)
 
 
 class MeasuresLocal(MeasuresBase, LocalTask):
     pass
 
 
-def _read_u64(path, key):
-    with vu.file_reader(path, 'r') as f:
-        a = f[key][:]
-    if a.dtype.kind not in 'ui':
-        raise ValueError('%s/%s: integer labels expected, got %s' % (path, key, a.dtype))
-    return np.ascontiguousarray(a.astype(np.uint64, copy=False))
-
-
 def measures(job_id, config_path):
-    import torch
-    from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
-    seg = _read_u64(config['seg_path'], config['seg_key'])
-    gt = _read_u64(config['gt_path'], config['gt_key'])
-    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-        r = ctx.evaluate(torch.from_numpy(seg.view(np.int64)).cuda(), torch.from_numpy(gt.view(np.int64)).cuda(),
+    config = fu.job_config(job_id, config_path)
+    seg = read_labels_u64(config['seg_path'], config['seg_key'])
+    gt = read_labels_u64(config['gt_path'], config['gt_key'])
+    with job_context() as (ctx, dev):
+        r = ctx.evaluate(labels_to_device(seg, dev), labels_to_device(gt, dev),
                          config['block_shape'], ignore_label=config['ignore_label'])
     fu.log('contingency table: %i pairs over %i points' % (r['n_pairs'], r['n_points']))
     results = {'vi-split': r['vi_split'], 'vi-merge': r['vi_merge'],
@@ -87,8 +66,4 @@ def measures(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    measures(job_id, path)
+    fu.run_job(measures)

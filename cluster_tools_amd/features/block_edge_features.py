@@ -21,7 +21,6 @@ Context.edge_features(raw=True) or Context.affinity_features(raw=True), goes to
 output_path:s0/sub_features is not created: its only reader is the reference's own merge job.  The
 costs and multicut stages are not built.
 """
-import json
 import os
 
 import numpy as np
@@ -31,6 +30,7 @@ from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 from cluster_tools_amd.graph.initial_sub_graphs import SUB_GRAPH_KEY
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context, read_labels_u64, labels_to_device
 
 NOT_BUILT = '%s is set in the block_edge_features task config: edge features from %s are not built%s'
 
@@ -50,9 +50,6 @@ class BlockEdgeFeaturesBase(Task):
     graph_path = Parameter()
     output_path = Parameter()
     dependency = TaskParameter(default=DummyTask())
-
-    def requires(self):
-        return self.dependency
 
     @staticmethod
     def default_task_config():
@@ -89,11 +86,7 @@ class BlockEdgeFeaturesBase(Task):
                        'output_path': self.output_path, 'block_shape': list(block_shape),
                        'graph_path': self.graph_path, 'ignore_label': ignore_label, 'tmp_folder': self.tmp_folder})
         block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end)
-        n_jobs = 1                     # one GPU job covers the volume
-        self.prepare_jobs(n_jobs, block_list, config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(1, block_list, config)     # one GPU job covers the volume
 
 
 class BlockEdgeFeaturesLocal(BlockEdgeFeaturesBase, LocalTask):
@@ -102,13 +95,8 @@ class BlockEdgeFeaturesLocal(BlockEdgeFeaturesBase, LocalTask):
 
 def block_edge_features(job_id, config_path):
     import torch
-    from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
-    with vu.file_reader(config['labels_path'], 'r') as f:
-        labels = np.ascontiguousarray(f[config['labels_key']][:].astype(np.uint64, copy=False))
+    config = fu.job_config(job_id, config_path)
+    labels = read_labels_u64(config['labels_path'], config['labels_key'])
     offsets = config.get('offsets')
     with vu.file_reader(config['input_path'], 'r') as f:
         ds = f[config['input_key']]
@@ -118,15 +106,14 @@ def block_edge_features(job_id, config_path):
     input_ = np.ascontiguousarray(input_)
     assert input_.shape[input_.ndim - 3:] == labels.shape, \
         'input %s and labels %s differ in shape' % (input_.shape, labels.shape)
-    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-        dev = torch.from_numpy(labels.view(np.int64)).to(ctx.torch_device())
-        vals = torch.from_numpy(input_).to(ctx.torch_device())
+    with job_context() as (ctx, dev):
+        labels_dev = labels_to_device(labels, dev)
+        vals = torch.from_numpy(input_).to(dev)
         if offsets is None:
-            raw = ctx.edge_features(dev, vals, ignore_label=bool(config['ignore_label']), raw=True)
+            raw = ctx.edge_features(labels_dev, vals, ignore_label=bool(config['ignore_label']), raw=True)
         else:
-            raw = ctx.affinity_features(dev, vals, offsets, ignore_label=bool(config['ignore_label']), raw=True)
-    for b in config['block_list']:
-        fu.log_block_success(b)
+            raw = ctx.affinity_features(labels_dev, vals, offsets, ignore_label=bool(config['ignore_label']), raw=True)
+    fu.log_blocks_success(config['block_list'])
     save_path = raw_table_path(config['tmp_folder'])
     fu.log('saving results to %s' % save_path)
     np.savez(save_path, **raw)
@@ -134,8 +121,4 @@ def block_edge_features(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    block_edge_features(job_id, path)
+    fu.run_job(block_edge_features)

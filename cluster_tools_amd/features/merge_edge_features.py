@@ -15,7 +15,6 @@ naming both -- and writes the table (_lib.edge_features_table).  A raw table wit
 (affinity features) has sample counts that are not the graph's sizes: only its edges are checked,
 and the dataset gets the attribute offsets beside the two others.
 """
-import json
 import os
 
 import numpy as np
@@ -41,9 +40,6 @@ class MergeEdgeFeaturesBase(Task):
     output_key = Parameter()
     dependency = TaskParameter(default=DummyTask())
 
-    def requires(self):
-        return self.dependency
-
     def run_impl(self):
         shebang = self.global_config_values()[0]
         self.init(shebang)
@@ -53,11 +49,7 @@ class MergeEdgeFeaturesBase(Task):
         self._write_log('Merging edge features for %i edges' % n_edges)
         config.update({'graph_path': self.graph_path, 'graph_key': self.graph_key, 'output_path': self.output_path,
                        'output_key': self.output_key, 'n_edges': n_edges, 'tmp_folder': self.tmp_folder})
-        n_jobs = 1
-        self.prepare_jobs(n_jobs, None, config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(1, None, config)
 
 
 class MergeEdgeFeaturesLocal(MergeEdgeFeaturesBase, LocalTask):
@@ -82,10 +74,7 @@ def write_table(f, key, table, offsets=None):
 
 def merge_edge_features(job_id, config_path):
     from cluster_tools_amd._lib import edge_features_table
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     save_path = raw_table_path(config['tmp_folder'])
     with np.load(save_path) as saved:
         raw = {k: saved[k] for k in saved.files}
@@ -106,8 +95,4 @@ def merge_edge_features(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_edge_features(job_id, path)
+    fu.run_job(merge_edge_features)

@@ -19,7 +19,6 @@ import os
 import numpy as np
 
 from cluster_tools_amd.luigi_compat import Task, Parameter, IntParameter, TaskParameter
-from cluster_tools_amd.luigi_compat import LocalTarget
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 from cluster_tools_amd.features.region_features import RegionFeaturesBase, raw_table_path
 import cluster_tools_amd.utils.volume_utils as vu
@@ -36,9 +35,6 @@ class MergeRegionFeaturesBase(Task):
     number_of_labels = IntParameter()
     prefix = Parameter(default='')
     dependency = TaskParameter(default=DummyTask())
-
-    def requires(self):
-        return self.dependency
 
     def _features_config(self):
         """feature_names and ignore_label of the region_features task config"""
@@ -72,7 +68,7 @@ class MergeRegionFeaturesBase(Task):
         self.check_jobs(n_jobs, self.prefix)
 
     def output(self):
-        return LocalTarget(os.path.join(self.tmp_folder, self.task_name + '_%s.log' % self.prefix))
+        return self.prefixed_output(self.prefix)
 
 
 class MergeRegionFeaturesLocal(MergeRegionFeaturesBase, LocalTask):
@@ -81,10 +77,7 @@ class MergeRegionFeaturesLocal(MergeRegionFeaturesBase, LocalTask):
 
 def merge_region_features(job_id, config_path):
     from cluster_tools_amd._lib import region_features_table_rows
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     with np.load(raw_table_path(config['tmp_folder'], config['prefix'])) as saved:
         raw = {k: saved[k] for k in ('ids', 'count', 'sum', 'minimum', 'maximum')}
         uint8_input = bool(saved['uint8_input'])
@@ -104,8 +97,4 @@ def merge_region_features(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_region_features(job_id, path)
+    fu.run_job(merge_region_features)

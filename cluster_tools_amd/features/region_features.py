@@ -19,16 +19,15 @@ ignore label included, it is dropped when the table is made --, goes to
 varlen dataset <tmp>/region_features_tmp.n5:block_feats is not created: its per-block float32
 serialization is read by nobody but the reference's own merge job.
 """
-import json
 import os
 
 import numpy as np
 
 from cluster_tools_amd.luigi_compat import Task, Parameter, IntParameter, TaskParameter
-from cluster_tools_amd.luigi_compat import LocalTarget
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context, read_labels_u64, labels_to_device
 
 
 def raw_table_path(tmp_folder, prefix):
@@ -46,9 +45,6 @@ class RegionFeaturesBase(Task):
     channel = IntParameter(default=None)
     prefix = Parameter(default='')
     dependency = TaskParameter(default=DummyTask())
-
-    def requires(self):
-        return self.dependency
 
     @staticmethod
     def default_task_config():
@@ -84,7 +80,7 @@ class RegionFeaturesBase(Task):
         self.check_jobs(n_jobs, self.prefix)
 
     def output(self):
-        return LocalTarget(os.path.join(self.tmp_folder, self.task_name + '_%s.log' % self.prefix))
+        return self.prefixed_output(self.prefix)
 
 
 class RegionFeaturesLocal(RegionFeaturesBase, LocalTask):
@@ -93,14 +89,9 @@ class RegionFeaturesLocal(RegionFeaturesBase, LocalTask):
 
 def region_features(job_id, config_path):
     import torch
-    from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     channel = config['channel']
-    with vu.file_reader(config['labels_path'], 'r') as f:
-        labels = np.ascontiguousarray(f[config['labels_key']][:].astype(np.uint64, copy=False))
+    labels = read_labels_u64(config['labels_path'], config['labels_key'])
     with vu.file_reader(config['input_path'], 'r') as f:
         ds = f[config['input_key']]
         input_ = ds[:] if channel is None else ds[channel:channel + 1].reshape(tuple(ds.shape)[1:])
@@ -108,12 +99,9 @@ def region_features(job_id, config_path):
         input_ = input_.astype('float32')
     input_ = np.ascontiguousarray(input_)
     assert input_.shape == labels.shape, 'input %s and labels %s differ in shape' % (input_.shape, labels.shape)
-    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-        dev = torch.from_numpy(labels.view(np.int64)).to(ctx.torch_device())
-        vals = torch.from_numpy(input_).to(ctx.torch_device())
-        raw = ctx.region_features(dev, vals, raw=True)
-    for b in config['block_list']:
-        fu.log_block_success(b)
+    with job_context() as (ctx, dev):
+        raw = ctx.region_features(labels_to_device(labels, dev), torch.from_numpy(input_).to(dev), raw=True)
+    fu.log_blocks_success(config['block_list'])
     save_path = raw_table_path(config['tmp_folder'], config['prefix'])
     fu.log('saving results to %s' % save_path)
     np.savez(save_path, uint8_input=np.array(input_.dtype == np.dtype('uint8')), **raw)
@@ -121,8 +109,4 @@ def region_features(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    region_features(job_id, path)
+    fu.run_job(region_features)

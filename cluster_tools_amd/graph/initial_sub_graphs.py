@@ -12,7 +12,6 @@ reference's per-block varlen datasets s0/sub_graphs/nodes and s0/sub_graphs/edge
 created: nifty's serialization of a block's sub-graph is read by nobody but nifty's own later
 stages (mergeSubgraphs, mapEdgeIds).
 """
-import json
 import os
 
 import numpy as np
@@ -21,6 +20,7 @@ from cluster_tools_amd.luigi_compat import Task, Parameter, TaskParameter
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context, read_labels_u64, labels_to_device
 
 SUB_GRAPH_KEY = 's0/sub_graphs'
 
@@ -37,9 +37,6 @@ class InitialSubGraphsBase(Task):
     input_key = Parameter()
     graph_path = Parameter()
     dependency = TaskParameter(default=DummyTask())
-
-    def requires(self):
-        return self.dependency
 
     @staticmethod
     def default_task_config():
@@ -61,11 +58,7 @@ class InitialSubGraphsBase(Task):
             g.attrs['shape'] = [int(s) for s in shape]
             g.attrs['ignore_label'] = bool(config['ignore_label'])
         block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end)
-        n_jobs = 1                     # one GPU job covers the volume
-        self.prepare_jobs(n_jobs, block_list, config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(1, block_list, config)     # one GPU job covers the volume
 
 
 class InitialSubGraphsLocal(InitialSubGraphsBase, LocalTask):
@@ -73,19 +66,11 @@ class InitialSubGraphsLocal(InitialSubGraphsBase, LocalTask):
 
 
 def initial_sub_graphs(job_id, config_path):
-    import torch
-    from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
-    with vu.file_reader(config['input_path'], 'r') as f:
-        labels = np.ascontiguousarray(f[config['input_key']][:].astype(np.uint64, copy=False))
-    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-        dev = torch.from_numpy(labels.view(np.int64)).to(ctx.torch_device())
-        graph = ctx.region_graph(dev, ignore_label=bool(config.get('ignore_label', True)))
-    for b in config['block_list']:
-        fu.log_block_success(b)
+    config = fu.job_config(job_id, config_path)
+    labels = read_labels_u64(config['input_path'], config['input_key'])
+    with job_context() as (ctx, dev):
+        graph = ctx.region_graph(labels_to_device(labels, dev), ignore_label=bool(config.get('ignore_label', True)))
+    fu.log_blocks_success(config['block_list'])
     save_path = raw_graph_path(config['tmp_folder'])
     fu.log('saving results to %s' % save_path)
     np.savez(save_path, **graph)
@@ -93,8 +78,4 @@ def initial_sub_graphs(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    initial_sub_graphs(job_id, path)
+    fu.run_job(initial_sub_graphs)

@@ -12,7 +12,6 @@ its row in graph_path:input_key/edges.
 import os
 
 from cluster_tools_amd.luigi_compat import Task, Parameter, IntParameter, TaskParameter
-from cluster_tools_amd.luigi_compat import LocalTarget
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 
 
@@ -26,15 +25,12 @@ class MapEdgeIdsBase(Task):
     scale = IntParameter()
     dependency = TaskParameter(default=DummyTask())
 
-    def requires(self):
-        return self.dependency
-
     def run_impl(self):
         self._write_log('per-block sub-graphs are not produced, no edge ids to map at scale %i: the id of an edge '
                         'is its row in %s:%s/edges' % (self.scale, self.graph_path, self.input_key))
 
     def output(self):
-        return LocalTarget(os.path.join(self.tmp_folder, self.task_name + '_s%i.log' % self.scale))
+        return self.prefixed_output('s%i' % self.scale)
 
 
 class MapEdgeIdsLocal(MapEdgeIdsBase, LocalTask):

@@ -23,13 +23,11 @@ its log only, with one line that says so; the complete graph comes from the whol
 whatever n_scales is.  Both kinds of task share the log target of their scale, as in the
 reference; the complete merge also counts as done only once the graph is written.
 """
-import json
 import os
 
 import numpy as np
 
 from cluster_tools_amd.luigi_compat import Task, Parameter, IntParameter, BoolParameter, TaskParameter
-from cluster_tools_amd.luigi_compat import LocalTarget
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 from cluster_tools_amd.graph.initial_sub_graphs import SUB_GRAPH_KEY, raw_graph_path
 import cluster_tools_amd.utils.volume_utils as vu
@@ -47,9 +45,6 @@ class MergeSubGraphsBase(Task):
     output_key = Parameter()
     merge_complete_graph = BoolParameter(default=False)
     dependency = TaskParameter(default=DummyTask())
-
-    def requires(self):
-        return self.dependency
 
     def _graph_written(self):
         if not os.path.isdir(self.graph_path):
@@ -76,14 +71,10 @@ class MergeSubGraphsBase(Task):
             g.attrs['shape'] = shape
         config.update({'graph_path': self.graph_path, 'scale': self.scale, 'output_key': self.output_key,
                        'merge_complete_graph': True, 'tmp_folder': self.tmp_folder})
-        n_jobs = 1
-        self.prepare_jobs(n_jobs, None, config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(1, None, config)
 
     def output(self):
-        return LocalTarget(os.path.join(self.tmp_folder, self.task_name + '_s%i.log' % self.scale))
+        return self.prefixed_output('s%i' % self.scale)
 
 
 class MergeSubGraphsLocal(MergeSubGraphsBase, LocalTask):
@@ -117,10 +108,7 @@ def read_graph(group):
 
 
 def merge_sub_graphs(job_id, config_path):
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     assert config['merge_complete_graph']
     with np.load(raw_graph_path(config['tmp_folder'])) as saved:
         graph = {k: saved[k] for k in ('nodes', 'edges', 'sizes')}
@@ -132,8 +120,4 @@ def merge_sub_graphs(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_sub_graphs(job_id, path)
+    fu.run_job(merge_sub_graphs)

@@ -12,16 +12,15 @@ cc_morphology; one GPU job covers the whole volume.  Its result, the exact (n, 1
 dataset at output_path / output_key is not created: its chunk layout is nifty's private
 serialization, read by nobody but nifty's mergeAndSerializeMorphology.
 """
-import json
 import os
 
 import numpy as np
 
 from cluster_tools_amd.luigi_compat import Task, Parameter, TaskParameter
-from cluster_tools_amd.luigi_compat import LocalTarget
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context, read_labels_u64, labels_to_device
 
 
 def raw_table_path(tmp_folder, prefix):
@@ -38,9 +37,6 @@ class BlockMorphologyBase(Task):
     output_key = Parameter()
     prefix = Parameter()
     dependency = TaskParameter(default=DummyTask())
-
-    def requires(self):
-        return self.dependency
 
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end = self.global_config_values()
@@ -60,7 +56,7 @@ class BlockMorphologyBase(Task):
         self.check_jobs(n_jobs, self.prefix)
 
     def output(self):
-        return LocalTarget(os.path.join(self.tmp_folder, '%s_%s.log' % (self.task_name, self.prefix)))
+        return self.prefixed_output(self.prefix)
 
 
 class BlockMorphologyLocal(BlockMorphologyBase, LocalTask):
@@ -68,20 +64,12 @@ class BlockMorphologyLocal(BlockMorphologyBase, LocalTask):
 
 
 def block_morphology(job_id, config_path):
-    import torch
-    from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
-    with vu.file_reader(config['input_path'], 'r') as f:
-        labels = np.ascontiguousarray(f[config['input_key']][:].astype(np.uint64, copy=False))
+    config = fu.job_config(job_id, config_path)
+    labels = read_labels_u64(config['input_path'], config['input_key'])
     assert labels.ndim == 3, 'the morphology table is defined for 3-D label volumes'
-    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-        dev = torch.from_numpy(labels.view(np.int64)).to(ctx.torch_device())
-        rows = ctx.morphology(dev, raw=True)
-    for b in config['block_list']:
-        fu.log_block_success(b)
+    with job_context() as (ctx, dev):
+        rows = ctx.morphology(labels_to_device(labels, dev), raw=True)
+    fu.log_blocks_success(config['block_list'])
     save_path = raw_table_path(config['tmp_folder'], config['prefix'])
     fu.log('saving results to %s' % save_path)
     np.save(save_path, rows)
@@ -89,8 +77,4 @@ def block_morphology(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    block_morphology(job_id, path)
+    fu.run_job(block_morphology)

@@ -11,13 +11,11 @@ job_prefix = prefix, the float64 gzip output dataset (number_of_labels, 11) with
 input_key, which is not created here -- and writes the rows of its id chunks (the centre of
 mass = coordinate sum / size; ids that do not occur: _lib.morphology_table).
 """
-import json
 import os
 
 import numpy as np
 
 from cluster_tools_amd.luigi_compat import Task, Parameter, IntParameter, TaskParameter
-from cluster_tools_amd.luigi_compat import LocalTarget
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 from cluster_tools_amd.morphology.block_morphology import raw_table_path
 import cluster_tools_amd.utils.volume_utils as vu
@@ -37,9 +35,6 @@ class MergeMorphologyBase(Task):
     prefix = Parameter()
     dependency = TaskParameter(default=DummyTask())
 
-    def requires(self):
-        return self.dependency
-
     def run_impl(self):
         shebang = self.global_config_values()[0]
         self.init(shebang)
@@ -54,14 +49,10 @@ class MergeMorphologyBase(Task):
                        'output_path': self.output_path, 'output_key': self.output_key,
                        'out_shape': out_shape, 'out_chunks': out_chunks,
                        'tmp_folder': self.tmp_folder, 'prefix': self.prefix})
-        n_jobs = min(len(block_list), self.max_jobs)
-        self.prepare_jobs(n_jobs, block_list, config, self.prefix)
-        self.submit_jobs(n_jobs, self.prefix)
-        self.wait_for_jobs(self.prefix)
-        self.check_jobs(n_jobs, self.prefix)
+        self.run_jobs(min(len(block_list), self.max_jobs), block_list, config, self.prefix)
 
     def output(self):
-        return LocalTarget(os.path.join(self.tmp_folder, self.task_name + '_%s.log' % self.prefix))
+        return self.prefixed_output(self.prefix)
 
 
 class MergeMorphologyLocal(MergeMorphologyBase, LocalTask):
@@ -70,10 +61,7 @@ class MergeMorphologyLocal(MergeMorphologyBase, LocalTask):
 
 def merge_morphology(job_id, config_path):
     from cluster_tools_amd._lib import morphology_table_rows
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     out_shape, out_chunks = config['out_shape'], config['out_chunks']
     raw = np.load(raw_table_path(config['tmp_folder'], config['prefix']))
     blocking = vu.Blocking([0], out_shape[:1], out_chunks[:1])
@@ -88,8 +76,4 @@ def merge_morphology(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_morphology(job_id, path)
+    fu.run_job(merge_morphology)

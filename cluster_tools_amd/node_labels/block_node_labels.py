@@ -17,15 +17,15 @@ temporary dataset, which only nifty reads, are not written.
 Not supported (each raises): a label volume smaller than the ws volume (the reference's
 ResizedVolume, :201-204), label-multiset ws datasets (:216-217) and a roi.
 """
-import json
 import os
 
 import numpy as np
 
-from cluster_tools_amd.luigi_compat import Task, Parameter, IntParameter, TaskParameter, LocalTarget
+from cluster_tools_amd.luigi_compat import Task, Parameter, IntParameter, TaskParameter
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context, labels_to_device
 
 
 def raw_overlaps_path(tmp_folder, key):
@@ -46,9 +46,6 @@ class BlockNodeLabelsBase(Task):
     ignore_label = IntParameter(default=None)
     prefix = Parameter(default='')
     dependency = TaskParameter(default=DummyTask())
-
-    def requires(self):
-        return self.dependency
 
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end = self.global_config_values()
@@ -83,14 +80,10 @@ class BlockNodeLabelsBase(Task):
                                        compression='gzip')
             ds_out.attrs['maxId'] = int(max_id)      # for MergeNodeLabels
         block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end)
-        n_jobs = 1                     # one GPU job covers the volume
-        self.prepare_jobs(n_jobs, block_list, config, self.prefix)
-        self.submit_jobs(n_jobs, self.prefix)
-        self.wait_for_jobs(self.prefix)
-        self.check_jobs(n_jobs, self.prefix)
+        self.run_jobs(1, block_list, config, self.prefix)     # one GPU job covers the volume
 
     def output(self):
-        return LocalTarget(os.path.join(self.tmp_folder, self.task_name + '_%s.log' % self.prefix))
+        return self.prefixed_output(self.prefix)
 
 
 class BlockNodeLabelsLocal(BlockNodeLabelsBase, LocalTask):
@@ -111,12 +104,7 @@ def _device_labels(a):
 
 
 def block_node_labels(job_id, config_path):
-    import torch
-    from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     ignore_label = config['ignore_label']
     with vu.file_reader(config['ws_path'], 'r') as f:
         ds_ws = f[config['ws_key']]
@@ -132,12 +120,10 @@ def block_node_labels(job_id, config_path):
         fu.log('accumulating labels without ignore label')
     else:
         fu.log('accumulating labels with ignore label %i' % ignore_label)
-    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-        dev = ctx.torch_device()
-        table = ctx.label_overlaps(torch.from_numpy(ws.view(np.int64)).to(dev), _device_labels(labels).to(dev),
+    with job_context() as (ctx, dev):
+        table = ctx.label_overlaps(labels_to_device(ws, dev), _device_labels(labels).to(dev),
                                    block_shape=config['block_shape'], ignore_label=ignore_label)
-    for b in config['block_list']:
-        fu.log_block_success(b)
+    fu.log_blocks_success(config['block_list'])
     save_path = raw_overlaps_path(config['tmp_folder'], config['output_key'])
     fu.log('saving %i overlaps to %s' % (len(table['counts']), save_path))
     np.savez(save_path, **table)
@@ -145,8 +131,4 @@ def block_node_labels(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    block_node_labels(job_id, path)
+    fu.run_job(block_node_labels)

@@ -19,12 +19,11 @@ output_path:output_key is a group with the 1-D uint64 datasets offsets (maxId + 
 counts -- node i overlaps labels[offsets[i]:offsets[i + 1]] (ascending) with counts[...] voxels --
 and the attribute maxId.  Datasets without an entry have shape (0,) and hold no chunk.
 """
-import json
 import os
 
 import numpy as np
 
-from cluster_tools_amd.luigi_compat import Task, Parameter, IntParameter, BoolParameter, TaskParameter, LocalTarget
+from cluster_tools_amd.luigi_compat import Task, Parameter, IntParameter, BoolParameter, TaskParameter
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 from cluster_tools_amd.node_labels.block_node_labels import raw_overlaps_path
 import cluster_tools_amd.utils.volume_utils as vu
@@ -49,9 +48,6 @@ class MergeNodeLabelsBase(Task):
     prefix = Parameter(default='')
     dependency = TaskParameter(default=DummyTask())
 
-    def requires(self):
-        return self.dependency
-
     def _job_prefix(self):
         return ('max_ol' if self.max_overlap else 'all_ol') + '_%s' % self.prefix
 
@@ -75,14 +71,10 @@ class MergeNodeLabelsBase(Task):
                 f.require_dataset(self.output_key, shape=node_shape, chunks=node_chunks, compression='gzip',
                                   dtype='uint64')
         prefix = self._job_prefix()
-        n_jobs = 1
-        self.prepare_jobs(n_jobs, None, config, prefix)
-        self.submit_jobs(n_jobs, prefix)
-        self.wait_for_jobs(prefix)
-        self.check_jobs(n_jobs, prefix)
+        self.run_jobs(1, None, config, prefix)
 
     def output(self):
-        return LocalTarget(os.path.join(self.tmp_folder, self.task_name + '_%s.log' % self._job_prefix()))
+        return self.prefixed_output(self._job_prefix())
 
 
 class MergeNodeLabelsLocal(MergeNodeLabelsBase, LocalTask):
@@ -112,10 +104,7 @@ def read_overlaps_csr(group):
 
 def merge_node_labels(job_id, config_path):
     from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     number_of_labels = int(config['node_shape'][0])
     with np.load(raw_overlaps_path(config['tmp_folder'], config['input_key'])) as saved:
         table = {k: saved[k] for k in _lib.LABEL_OVERLAPS}
@@ -135,8 +124,4 @@ def merge_node_labels(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_node_labels(job_id, path)
+    fu.run_job(merge_node_labels)

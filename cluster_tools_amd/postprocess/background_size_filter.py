@@ -15,7 +15,6 @@ call also relabels the filtered volume consecutively (find_labeling.py:106-116),
 the (m, 2) assignment table to output_path/<assignment_key> and sets `maxId` to the new maximum
 -- the RelabelWorkflow the reference chains behind the filter, without its three more passes.
 """
-import json
 import os
 
 import numpy as np
@@ -24,6 +23,7 @@ from cluster_tools_amd.luigi_compat import Task, Parameter, BoolParameter, TaskP
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context, labels_to_device
 
 
 class BackgroundSizeFilterBase(Task):
@@ -37,9 +37,6 @@ class BackgroundSizeFilterBase(Task):
     relabel = BoolParameter(default=False)
     assignment_key = Parameter(default='relabel_size_filter')
     dependency = TaskParameter(default=DummyTask())
-
-    def requires(self):
-        return self.dependency
 
     def _parse_log(self, log_path):
         with open(log_path) as f:
@@ -68,11 +65,7 @@ class BackgroundSizeFilterBase(Task):
         if self.relabel:
             config.update({'relabel': True, 'assignment_key': self.assignment_key})
         self._write_log('scheduling %i blocks to be processed' % len(block_list))
-        n_jobs = 1                     # one GPU job filters the volume
-        self.prepare_jobs(n_jobs, block_list, config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(1, block_list, config)     # one GPU job filters the volume
 
 
 class BackgroundSizeFilterLocal(BackgroundSizeFilterBase, LocalTask):
@@ -80,12 +73,7 @@ class BackgroundSizeFilterLocal(BackgroundSizeFilterBase, LocalTask):
 
 
 def background_size_filter(job_id, config_path):
-    import torch
-    from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     input_path, input_key = config['input_path'], config['input_key']
     output_path, output_key = config['output_path'], config['output_key']
     block_list, block_shape = config['block_list'], config['block_shape']
@@ -96,9 +84,8 @@ def background_size_filter(job_id, config_path):
         labels = np.ascontiguousarray(f[input_key][:].astype(np.uint64, copy=False))
         max_id = f[input_key].attrs.get('maxId', None)
     shape = labels.shape
-    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-        dev = torch.from_numpy(labels.view(np.int64)).to(ctx.torch_device())
-        out, info = ctx.size_filter(dev, discard_ids=discard_ids, relabel=relabel)
+    with job_context() as (ctx, dev):
+        out, info = ctx.size_filter(labels_to_device(labels, dev), discard_ids=discard_ids, relabel=relabel)
         out = out.cpu().numpy().view(np.uint64)
     blocking = vu.Blocking([0, 0, 0], list(shape), block_shape)
     with vu.file_reader(output_path) as f:
@@ -127,8 +114,4 @@ def background_size_filter(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    background_size_filter(job_id, path)
+    fu.run_job(background_size_filter)

@@ -10,7 +10,6 @@ the per-job (ids, counts) without the reference's dense np.zeros(uniques[-1] + 1
 sparse 64-bit ids are fine.  target_number: the reference's order among equal counts is an
 unstable argsort; here the larger id ranks first (as cc_size_filter does).
 """
-import json
 import os
 
 import numpy as np
@@ -30,9 +29,6 @@ class SizeFilterBlocksBase(Task):
     size_threshold = IntParameter(default=None)
     target_number = IntParameter(default=None)
     dependency = TaskParameter(default=DummyTask())
-
-    def requires(self):
-        return self.dependency
 
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end = self.global_config_values()
@@ -79,10 +75,7 @@ def select_discard_ids(uniques, counts, size_threshold=None, target_number=None)
 
 
 def size_filter_blocks(job_id, config_path):
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     n_jobs, tmp_folder = config['n_jobs'], config['tmp_folder']
     unique_values = [np.load(os.path.join(tmp_folder, 'find_uniques_job_%i.npy' % j)) for j in range(n_jobs)]
     count_values = [np.load(os.path.join(tmp_folder, 'counts_job_%i.npy' % j)) for j in range(n_jobs)]
@@ -101,8 +94,4 @@ def size_filter_blocks(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    size_filter_blocks(job_id, path)
+    fu.run_job(size_filter_blocks)

@@ -9,7 +9,6 @@ with return_counts, <tmp>/counts_job_<i>.npy (uint64 voxel counts), and the job 
 job's blocks, find_uniques.py:105-177) runs on the MI355X through cc_label_sizes; one GPU job
 counts the whole volume, so there is one artefact pair (job 0).
 """
-import json
 import os
 
 import numpy as np
@@ -18,6 +17,7 @@ from cluster_tools_amd.luigi_compat import Task, Parameter, BoolParameter, TaskP
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context, read_labels_u64, labels_to_device
 
 
 class FindUniquesBase(Task):
@@ -29,23 +29,16 @@ class FindUniquesBase(Task):
     return_counts = BoolParameter(default=False)
     dependency = TaskParameter(default=DummyTask())
 
-    def requires(self):
-        return self.dependency
-
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end, block_list_path = \
             self.global_config_values(with_block_list_path=True)
         self.init(shebang)
         shape = vu.get_shape(self.input_path, self.input_key)
         block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end, block_list_path=block_list_path)
-        n_jobs = 1                     # one GPU job counts the volume
         config = {'input_path': self.input_path, 'input_key': self.input_key, 'block_shape': block_shape,
                   'tmp_folder': self.tmp_folder, 'return_counts': bool(self.return_counts)}
         self._write_log('scheduling %i blocks to be processed' % len(block_list))
-        self.prepare_jobs(n_jobs, block_list, config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(1, block_list, config)     # one GPU job counts the volume
 
 
 class FindUniquesLocal(FindUniquesBase, LocalTask):
@@ -53,20 +46,12 @@ class FindUniquesLocal(FindUniquesBase, LocalTask):
 
 
 def find_uniques(job_id, config_path):
-    import torch
-    from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     tmp_folder = config['tmp_folder']
-    with vu.file_reader(config['input_path'], 'r') as f:
-        labels = np.ascontiguousarray(f[config['input_key']][:].astype(np.uint64, copy=False))
-    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-        dev = torch.from_numpy(labels.view(np.int64)).to(ctx.torch_device())
-        unique_values, counts = ctx.label_sizes(dev)
-    for b in config['block_list']:
-        fu.log_block_success(b)
+    labels = read_labels_u64(config['input_path'], config['input_key'])
+    with job_context() as (ctx, dev):
+        unique_values, counts = ctx.label_sizes(labels_to_device(labels, dev))
+    fu.log_blocks_success(config['block_list'])
     if config['return_counts']:
         np.save(os.path.join(tmp_folder, 'counts_job_%i.npy' % job_id), counts)
     save_path = os.path.join(tmp_folder, 'find_uniques_job_%i.npy' % job_id)
@@ -76,8 +61,4 @@ def find_uniques(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    find_uniques(job_id, path)
+    fu.run_job(find_uniques)

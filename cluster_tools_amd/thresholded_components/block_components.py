@@ -27,6 +27,7 @@ from cluster_tools_amd.luigi_compat import Task, Parameter, FloatParameter, Task
 from cluster_tools_amd.cluster_tasks import LocalTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context
 
 FUSED_MARKER = 'cc_fused.json'
 FUSED_LUT = 'cc_fused_assignments.npy'
@@ -59,9 +60,6 @@ class BlockComponentsBase(Task):
         config = LocalTask.default_task_config()
         config.update({'sigma_prefilter': 0, 'gpus': 1, 'dist_backend': 'nccl'})
         return config
-
-    def requires(self):
-        return self.dependency
 
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end = self.global_config_values()
@@ -102,11 +100,7 @@ class BlockComponentsBase(Task):
         with vu.file_reader(self.output_path) as f:
             f.require_dataset(self.output_key, shape=shape, dtype='uint64', compression=compression, chunks=chunks)
         block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end)
-        n_jobs = 1
-        self.prepare_jobs(n_jobs, block_list, config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(1, block_list, config)
 
 
 class BlockComponentsLocal(BlockComponentsBase, LocalTask):
@@ -258,12 +252,7 @@ def _fused_single(config, shape, nb):
     if chans is None and not resized and sigma <= 0 and not config.get('torch_path', False):
         return _fused_host(config, shape, nb, inp, mask, timing)
     import torch
-    from cluster_tools_amd import _lib
-    device = int(os.environ.get('CC_DEVICE', '0'))
-    dev = torch.device('cuda', device)
-    torch.cuda.set_device(dev)
-    with _lib.Context(device) as ctx:
-        ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    with job_context(torch_stream=True) as (ctx, dev):
         ctx.set_empty_job_quirk(config.get('quirk_jobs', 0))
         t = time.perf_counter()
         if chans is None:
@@ -350,10 +339,7 @@ def _fused_sharded(config_path, config, shape, nb):
 
 
 def block_components(job_id, config_path):
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     block_list = config['block_list']
     tmp_folder = config['tmp_folder']
     block_shape = config['block_shape']
@@ -379,26 +365,20 @@ def block_components(job_id, config_path):
             values, lut, res, timing = _fused_single(config, shape, nb)
         _write_fused_artefacts(tmp_folder, config, values, lut, res, timing)
     else:
-        import torch
-        from cluster_tools_amd import _lib
         inp, chans = read_input(config)
         mask, resized = read_mask(config, shape)
-        with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-            x = to_device(ctx, inp, chans, ctx.torch_device(), config)
-            m = device_mask(ctx, mask, resized, shape, x.device)
+        with job_context() as (ctx, dev):
+            x = to_device(ctx, inp, chans, dev, config)
+            m = device_mask(ctx, mask, resized, shape, dev)
             lab_dev, values = ctx.block_components(x, block_shape, threshold, mode, m)
             labels = lab_dev.cpu().numpy().view(np.uint64)
         _write_output(config, labels, [(0, s) for s in shape])
-    for b in block_list:
-        fu.log_block_success(b)
-    offsets = {b: int(values[b]) for b in block_list}
+    fu.log_blocks_success(block_list)
+    offsets ={b: int(values[b]) for b in block_list}
     with open(os.path.join(tmp_folder, 'connected_components_offsets_%i.json' % job_id), 'w') as f:
         json.dump(offsets, f)
     fu.log_job_success(job_id)
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    block_components(job_id, path)
+    fu.run_job(block_components)

@@ -11,7 +11,6 @@ and if any of them has no block with an upper-face pair the LUT is the identity.
 BlockComponents job applies the same rule on the device (CC_OPT_EMPTY_JOB_QUIRK)."""
 import json
 import os
-import sys
 
 import numpy as np
 
@@ -19,6 +18,7 @@ from cluster_tools_amd.luigi_compat import Task, Parameter, ListParameter, TaskP
 from cluster_tools_amd.cluster_tasks import LocalTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context
 from cluster_tools_amd.thresholded_components.block_components import FUSED_MARKER, FUSED_LUT
 
 
@@ -46,9 +46,6 @@ class MergeAssignmentsBase(Task):
     save_prefix = Parameter(default='cc_assignments')
     dependency = TaskParameter()
 
-    def requires(self):
-        return self.dependency
-
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end = self.global_config_values()
         self.init(shebang)
@@ -56,10 +53,7 @@ class MergeAssignmentsBase(Task):
         config.update({'output_path': self.output_path, 'output_key': self.output_key,
                        'tmp_folder': self.tmp_folder, 'n_jobs': 1, 'offset_path': self.offset_path,
                        'save_prefix': self.save_prefix, 'max_jobs': int(self.max_jobs)})
-        self.prepare_jobs(1, None, config)
-        self.submit_jobs(1)
-        self.wait_for_jobs()
-        self.check_jobs(1)
+        self.run_jobs(1, None, config)
 
 
 class MergeAssignmentsLocal(MergeAssignmentsBase, LocalTask):
@@ -67,10 +61,7 @@ class MergeAssignmentsLocal(MergeAssignmentsBase, LocalTask):
 
 
 def merge_assignments(job_id, config_path):
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     tmp_folder = config['tmp_folder']
     with open(config['offset_path']) as f:
         n_labels = int(json.load(f)['n_labels'])
@@ -80,7 +71,6 @@ def merge_assignments(job_id, config_path):
         assert len(lut) == n_labels, (len(lut), n_labels)
         fu.log('assignments from the fused BlockComponents job')
     else:
-        from cluster_tools_amd import _lib
         pairs = [np.load(os.path.join(tmp_folder, '%s_%i.npy' % (config['save_prefix'], j)))
                  for j in range(config['n_jobs'])]
         pairs = [p.reshape(-1, 2) for p in pairs if p.size]
@@ -93,7 +83,7 @@ def merge_assignments(job_id, config_path):
                    % min(len(np.load(flags_path)), config['max_jobs']))
             lut = np.arange(n_labels, dtype=np.uint64)
         else:
-            with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
+            with job_context() as (ctx, _):
                 lut = ctx.merge_assignments(pairs, n_labels)
     chunks = (min(65334, n_labels),)
     with vu.file_reader(config['output_path']) as f:
@@ -102,7 +92,4 @@ def merge_assignments(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_assignments(job_id, path)
+    fu.run_job(merge_assignments)

@@ -3,7 +3,6 @@
 Same inputs (per-job JSONs), same cc_offsets.json; the scan runs through cc_merge_offsets."""
 import json
 import os
-import sys
 
 import numpy as np
 
@@ -23,9 +22,6 @@ class MergeOffsetsBase(Task):
     save_prefix = Parameter(default='connected_components_offsets')
     dependency = TaskParameter()
 
-    def requires(self):
-        return self.dependency
-
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end = self.global_config_values()
         self.init(shebang)
@@ -34,10 +30,7 @@ class MergeOffsetsBase(Task):
         config = self.get_task_config()
         config.update({'tmp_folder': self.tmp_folder, 'n_jobs': n_jobs, 'save_path': self.save_path,
                        'n_blocks': len(block_list), 'save_prefix': self.save_prefix})
-        self.prepare_jobs(1, None, config)
-        self.submit_jobs(1)
-        self.wait_for_jobs()
-        self.check_jobs(1)
+        self.run_jobs(1, None, config)
 
 
 class MergeOffsetsLocal(MergeOffsetsBase, LocalTask):
@@ -47,10 +40,7 @@ class MergeOffsetsLocal(MergeOffsetsBase, LocalTask):
 def merge_offsets(job_id, config_path):
     from cluster_tools_amd import _lib
     _lib.load(host_only=True)         # a one-shot job process: host arithmetic only, no torch import
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     tmp_folder, n_jobs = config['tmp_folder'], config['n_jobs']
     n_blocks, save_prefix = config['n_blocks'], config['save_prefix']
     offsets = {}
@@ -74,7 +64,4 @@ def merge_offsets(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_offsets(job_id, path)
+    fu.run_job(merge_offsets)

@@ -11,15 +11,13 @@ the whole volume and writes the listed blocks.  channel (4-D input): the listed 
 averaged on the device first (cc_channel_mean, threshold.py:139-148); sigma_prefilter > 0: per block
 normalize + Gaussian smoothing first (cc_gaussian_smooth_blocks, threshold.py:150-153).
 """
-import json
 import os
-
-import numpy as np
 
 from cluster_tools_amd.luigi_compat import Task, Parameter, FloatParameter, TaskParameter
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context
 
 
 class ThresholdBase(Task):
@@ -43,9 +41,6 @@ class ThresholdBase(Task):
         config = LocalTask.default_task_config()
         config.update({'sigma_prefilter': 0})
         return config
-
-    def requires(self):
-        return self.dependency
 
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end, block_list_path = \
@@ -74,11 +69,7 @@ class ThresholdBase(Task):
         with vu.file_reader(self.output_path) as f:
             f.require_dataset(self.output_key, shape=shape, dtype='uint8', compression=compression, chunks=chunks)
         block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end)
-        n_jobs = 1                     # one GPU job thresholds the volume
-        self.prepare_jobs(n_jobs, block_list, config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(1, block_list, config)     # one GPU job thresholds the volume
 
 
 class ThresholdLocal(ThresholdBase, LocalTask):
@@ -86,12 +77,7 @@ class ThresholdLocal(ThresholdBase, LocalTask):
 
 
 def threshold(job_id, config_path):
-    import torch
-    from cluster_tools_amd import _lib
-    fu.log('start processing job %i' % job_id)
-    fu.log('reading config from %s' % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.job_config(job_id, config_path)
     block_list = config['block_list']
     block_shape = config['block_shape']
     thr, mode = config['threshold'], config['threshold_mode']
@@ -99,8 +85,8 @@ def threshold(job_id, config_path):
     from cluster_tools_amd.thresholded_components.block_components import read_input, to_device
     inp, chans = read_input(config)
     shape = inp.shape if chans is None else inp.shape[1:]
-    with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-        x = to_device(ctx, inp, chans, ctx.torch_device(), config)
+    with job_context() as (ctx, dev):
+        x = to_device(ctx, inp, chans, dev, config)
         out = ctx.threshold(x, block_shape, thr, mode).cpu().numpy()
     blocking = vu.Blocking([0, 0, 0], list(shape), block_shape)
     with vu.file_reader(config['output_path']) as f:
@@ -113,8 +99,4 @@ def threshold(job_id, config_path):
 
 
 if __name__ == '__main__':
-    import sys
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    threshold(job_id, path)
+    fu.run_job(threshold)

@@ -6,7 +6,6 @@ BlockComponents job, the relabel is skipped and only maxId and the logs are writ
 The dict / pickled-map and label-multiset branches of the reference are out of scope."""
 import json
 import os
-import sys
 
 import numpy as np
 
@@ -14,6 +13,7 @@ from cluster_tools_amd.luigi_compat import Task, Parameter, TaskParameter
 from cluster_tools_amd.cluster_tasks import LocalTask, DummyTask
 import cluster_tools_amd.utils.volume_utils as vu
 import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.device_utils import job_context, labels_to_device
 
 
 class WriteBase(Task):
@@ -29,9 +29,6 @@ class WriteBase(Task):
     dependency = TaskParameter(default=DummyTask())
     identifier = Parameter()
     offset_path = Parameter(default='')
-
-    def requires(self):
-        return self.dependency
 
     @staticmethod
     def default_task_config():
@@ -65,15 +62,10 @@ class WriteBase(Task):
             config.update({'output_path': self.output_path, 'output_key': self.output_key})
         block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end, block_list_path=block_list_path)
         self._write_log('scheduling %i blocks to be processed' % len(block_list))
-        n_jobs = 1
-        self.prepare_jobs(n_jobs, block_list, config, self.identifier)
-        self.submit_jobs(n_jobs, self.identifier)
-        self.wait_for_jobs(self.identifier)
-        self.check_jobs(n_jobs, self.identifier)
+        self.run_jobs(1, block_list, config, self.identifier)
 
     def output(self):
-        from cluster_tools_amd.luigi_compat import LocalTarget
-        return LocalTarget(os.path.join(self.tmp_folder, '%s_%s.log' % (self.task_name, self.identifier)))
+        return self.prefixed_output(self.identifier)
 
 
 class WriteLocal(WriteBase, LocalTask):
@@ -104,17 +96,15 @@ def write(job_id, config_path):
     if done:
         fu.log('labels already final (fused BlockComponents job)')
     else:
-        import torch
-        from cluster_tools_amd import _lib
         with vu.file_reader(input_path, 'r') as f:
             seg = f[input_key][:]
         shape = seg.shape
         nb = vu.Blocking([0, 0, 0], list(shape), block_shape).numberOfBlocks
         offs = offsets if offsets is not None else np.zeros(nb, dtype=np.uint64)
-        dev = torch.from_numpy(seg.view(np.int64)).cuda()
-        with _lib.Context(int(os.environ.get('CC_DEVICE', '0'))) as ctx:
-            ctx.write(dev, block_shape, offs, lut)
-        seg = dev.cpu().numpy().view(np.uint64)
+        with job_context() as (ctx, dev):
+            seg_dev = labels_to_device(seg, dev)
+            ctx.write(seg_dev, block_shape, offs, lut)
+        seg = seg_dev.cpu().numpy().view(np.uint64)
         blocking = vu.Blocking([0, 0, 0], list(shape), block_shape)
         with vu.file_reader(output_path) as f:
             ds = f[output_key]
@@ -133,7 +123,4 @@ def write(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    write(job_id, path)
+    fu.run_job(write)

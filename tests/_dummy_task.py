@@ -2,7 +2,6 @@
 """A trivial task on the cluster_tools_amd LocalTask framework (tests/test_task_framework.py)."""
 import json
 import os
-import sys
 
 from cluster_tools_amd.luigi_compat import Task, Parameter, TaskParameter
 from cluster_tools_amd.cluster_tasks import LocalTask
@@ -15,21 +14,18 @@ class DummyStageBase(Task):
     allow_retry = True
     out_path = Parameter()
     fail_first = Parameter(default='')
+    prefix = Parameter(default='')
     dependency = TaskParameter()
-
-    def requires(self):
-        return self.dependency
 
     def run_impl(self):
         shebang, block_shape, roi_begin, roi_end = self.global_config_values()
         self.init(shebang)
         config = self.get_task_config()
         config.update({'out_path': self.out_path, 'fail_first': self.fail_first, 'tmp_folder': self.tmp_folder})
-        n_jobs = min(4, self.max_jobs)
-        self.prepare_jobs(n_jobs, list(range(10)), config)
-        self.submit_jobs(n_jobs)
-        self.wait_for_jobs()
-        self.check_jobs(n_jobs)
+        self.run_jobs(min(4, self.max_jobs), list(range(10)), config, self.prefix or None)
+
+    def output(self):
+        return self.prefixed_output(self.prefix) if self.prefix else super().output()
 
 
 class DummyStageLocal(DummyStageBase, LocalTask):
@@ -52,6 +48,4 @@ def dummy_stage(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    dummy_stage(job_id, path)
+    fu.run_job(dummy_stage)

@@ -1,0 +1,53 @@
+#! /usr/bin/python
+"""The drop-in surface of every *Local task class of cluster_tools_amd, as JSON: task_name,
+allow_retry, the parameters with their defaults and default_task_config().
+
+    python tools/dump_task_surface.py > tests/golden/task_surface.json
+
+tests/test_task_framework.py rebuilds the same dict from the current classes and compares it with
+the committed dump, so regenerate the dump only where a task's surface is meant to change.
+"""
+import importlib
+import inspect
+import json
+import os
+import pkgutil
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import cluster_tools_amd  # noqa: E402
+from cluster_tools_amd.cluster_tasks import BaseClusterTask  # noqa: E402
+from cluster_tools_amd.luigi_compat import Parameter  # noqa: E402
+
+
+def _default(param):
+    d = getattr(param, 'default', getattr(param, '_default', None))
+    if d is None or isinstance(d, (bool, int, float, str)):
+        return d
+    if isinstance(d, (list, tuple)):
+        return list(d)
+    return type(d).__name__            # a task instance (dependency = DummyTask())
+
+
+def task_surface():
+    surface = {}
+    for info in pkgutil.walk_packages(cluster_tools_amd.__path__, 'cluster_tools_amd.'):
+        module = importlib.import_module(info.name)
+        for name, klass in inspect.getmembers(module, inspect.isclass):
+            if not (name.endswith('Local') and issubclass(klass, BaseClusterTask)
+                    and klass.__module__ == info.name):
+                continue
+            params = {}
+            for k in reversed(klass.__mro__):
+                params.update({n: _default(p) for n, p in vars(k).items() if isinstance(p, Parameter)})
+            surface['%s.%s' % (info.name, name)] = {
+                'task_name': klass.task_name, 'allow_retry': klass.allow_retry,
+                'parameters': dict(sorted(params.items())),
+                'default_task_config': klass.default_task_config()}
+    return dict(sorted(surface.items()))
+
+
+if __name__ == '__main__':
+    json.dump(task_surface(), sys.stdout, indent=1, sort_keys=True)
+    sys.stdout.write('\n')
