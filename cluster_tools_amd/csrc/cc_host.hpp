@@ -1,5 +1,5 @@
 // cc_host.hpp -- host-side helpers shared by the library (cc_lib.hip) and the kernel
-// ablation harness (tools/ablate.hip): error type, block grid + tile tables.
+// timing harness (tools/ablate.hip): error type, block grid + tile tables.
 #pragma once
 #include <cstdint>
 #include <initializer_list>

@@ -1,37 +1,42 @@
 // cc_kernels.hip -- gfx950 kernels of the thresholded connected-components path.
 //
-// Pipeline (one launch each; DESIGN.md §3 has the roofline per kernel):
-//   k_block_stats   per-block min / max / NaN of the f32 input            (volume_utils.py:98-105)
-//   k_block_params  per-block foreground interval in float order          (block_components.py:161-173)
-//   k_pass1         threshold+mask -> bit rows -> tile CCL in LDS -> nodes, face planes
-//   k_stitch<0>     26-connected unions across tile seams inside a block   (= block-local components)
-//   k_collect_roots block-local roots -> (block, first voxel) sort keys
-//   [radix sort]    -> skimage's raster first-occurrence numbering per block (block_components.py:179)
-//   k_segments / k_values / [scan] / k_assign_rid   merge_offsets.py:104-120 on the device
-//   k_stitch<1>     6-connected unions across block faces                 (block_faces.py:87-137,
-//                                                                          merge_assignments.py:105-130)
-//   k_lut           the 'assignments' LUT (min-id representative)
-//   k_finalize      final label per node
-//   k_pass2         bit rows -> tile CCL recomputed in LDS -> uint64 labels (write.py:185-202)
+// The pipeline cc_lib.hip launches (DESIGN.md §3 has the roofline per kernel):
+//   front (phase_local), one read of the input:
+//     k_sample + k_guess   per-block foreground interval guessed from a sparse sample (k_sample's
+//                          threads also clear the run's device state); masked runs: k_mask_live
+//     k_spec               per tile: exact block statistics (volume_utils.py:98-105) AND pass 1 under
+//                          the guess: threshold+mask -> bit rows -> tile CCL in LDS -> nodes, face planes
+//     k_params_verify      exact interval per block (block_components.py:161-173), lists the tiles
+//                          whose guessed bits are not exact
+//     k_fix                pass 1 again for the listed tiles
+//     k_seams              pairs of tile components across the tile seams, per tile (in z-layer
+//                          chunks behind k_spec, or once after k_fix; k_seams_list redoes marked tiles)
+//     k_block_uf           26-connected unions inside a block from those pairs, in LDS
+//                          (= block-local components), roots ranked by first voxel = skimage's
+//                          raster first-occurrence numbering per block (block_components.py:179)
+//   then one of two schedules (results never depend on which one ran):
+//     one read-back        k_scan_emit (or k_block_scan + k_emit_roots): block values, offsets and
+//                          rids on the device (merge_offsets.py:104-120), no host read; a run the
+//                          enqueued launches were not valid for raises redo flags (RF_*) and is redone
+//     host-synchronised    k_block_scan, a read of the root count and the flags, k_emit_roots
+//   generic fallback (a block the LDS union-find could not take, host-synchronised only):
+//     k_stitch<false>, k_count_roots, [scan], k_collect_roots, [radix sort], k_segments, k_values,
+//     [scan], k_nlabels, k_assign_rid
+//   block faces (rid_unions) and labels (phase_final):
+//     k_inter_union        6-connected unions across block faces from k_seams' lists (block_faces.py:87-137,
+//                          merge_assignments.py:105-130); overflowed lists: k_stitch<true>
+//     k_lut_all, k_status  the 'assignments' LUT (min-id representative), the run's one read-back
+//     k_pass2              bit rows -> tile CCL recomputed in LDS -> uint64 labels (write.py:185-202);
+//                          stage-level block_components: k_finalize<true> first
+//   The stand-alone Threshold task (cc_threshold): k_sample + k_guess, k_thr_spec, k_params_verify,
+//   k_thr_fix; or, two reads of the input, k_block_stats -> k_block_params -> k_threshold.
 #include "cc_common.hpp"
 #include "cc_rows.hpp"
 
 namespace cc {
 
-// ------------------------------------------------------------------------------------------
-// direction tables for the 13 lex-negative cube neighbours (dz, dy, dx)
-// cube mask bit index = lz*4 + ly*2 + lx
-// ------------------------------------------------------------------------------------------
-__host__ __device__ constexpr u32 sel_bits(int sz, int sy, int sx) {
-    // s: 0 -> local 0 only, 1 -> local 1 only, 2 -> both
-    u32 m = 0;
-    for (int lz = 0; lz < 2; ++lz)
-        for (int ly = 0; ly < 2; ++ly)
-            for (int lx = 0; lx < 2; ++lx)
-                if ((sz == 2 || sz == lz) && (sy == 2 || sy == ly) && (sx == 2 || sx == lx))
-                    m |= 1u << (lz * 4 + ly * 2 + lx);
-    return m;
-}
+// selections of a face cube's voxels towards a neighbour at offset d along one face axis
+// (0 -> local 0 only, 1 -> local 1 only, 2 -> both): own side, neighbour side
 __host__ __device__ constexpr int self_sel(int d) { return d < 0 ? 0 : d > 0 ? 1 : 2; }
 __host__ __device__ constexpr int nbr_sel(int d) { return d < 0 ? 1 : d > 0 ? 0 : 2; }
 // 4-bit face selection (layout p*2 + q)
@@ -42,14 +47,6 @@ __host__ __device__ constexpr u32 fsel(int sp, int sq) {
             if ((sp == 2 || sp == p) && (sq == 2 || sq == q)) m |= 1u << (p * 2 + q);
     return m;
 }
-
-#define CC_DIRS(X)                                                                            \
-    X(-1, -1, -1) X(-1, -1, 0) X(-1, -1, 1) X(-1, 0, -1) X(-1, 0, 0) X(-1, 0, 1) X(-1, 1, -1) \
-    X(-1, 1, 0) X(-1, 1, 1) X(0, -1, -1) X(0, -1, 0) X(0, -1, 1) X(0, 0, -1)
-// the same without (0, 0, -1), which the x-runs cover
-#define CC_DIRS12(X)                                                                          \
-    X(-1, -1, -1) X(-1, -1, 0) X(-1, -1, 1) X(-1, 0, -1) X(-1, 0, 0) X(-1, 0, 1) X(-1, 1, -1) \
-    X(-1, 1, 0) X(-1, 1, 1) X(0, -1, -1) X(0, -1, 0) X(0, -1, 1)
 
 // ------------------------------------------------------------------------------------------
 // Tile CCL in LDS.
@@ -124,22 +121,18 @@ __device__ __forceinline__ void load_row4(const u64* rows, int row, u64 a[4]) {
 __device__ __forceinline__ u32 run_of(const TileCCL& T, int row, int cx) {
     return T.roff[row] + (u32)__popc(T.B[row] & mask_le(cx)) - 1;
 }
-// run id of the run starting at cube cx0 (a set bit of B)
-__device__ __forceinline__ u32 run_at(const TileCCL& T, int row, int cx0) {
-    return T.roff[row] + (u32)__popc(T.B[row] & ((1u << cx0) - 1));
-}
 
 // Thread (row = tid / 4, q = tid % 4) owns the run starts in cubes [8q, 8q + 8) of cube row `row`,
 // so the per-run phases keep all 8 waves busy; tid order is run-id order.
-#ifndef CC_CCL_LIST
-#define CC_CCL_LIST 1
-#endif
-// list (nullable, LDS, capacity NRUN): phase 2 first lists its union pairs, then every thread takes
+// list (LDS, capacity NRUN): phase 2 first lists its union pairs, then every thread takes
 // an equal share of the list (each thread's own contacts vary from none to dozens: processed in
-// place they leave most lanes idle and the barrier waiting for the busiest row)
+// place they leave most lanes idle and the barrier waiting for the busiest row).  Every caller
+// passes a list, but the compiler does not fold `list != nullptr` for an LDS address, so the
+// in-place branch below is still compiled into k_spec, k_fix and k_pass2 and shapes their
+// register allocation (without it k_pass2 goes from 41 to 38 VGPRs and every instruction of the
+// three kernels moves): it stays until its removal is measured as a change of its own.
 // firstv (nullable, LDS, may alias list): firstv[k] = the first voxel (tile raster index) of
 // component k, computed in phase 5 from each run's first voxel (pass 1's keys).
-template <int STOP = 0>   // ablation harness only: return after phase STOP (1..3; 4: pair list only)
 __device__ __forceinline__ u32 tile_ccl(const u64* rows, TileCCL& T, u32* list = nullptr, u32* firstv = nullptr) {
     const int tid = cc_tid();
     const int qrow = tid >> 2, q = tid & 3;
@@ -159,9 +152,8 @@ __device__ __forceinline__ u32 tile_ccl(const u64* rows, TileCCL& T, u32* list =
         Bq = B & (0xFFu << (8 * q));
     }
     __syncthreads();
-    if (STOP == 1) return 0;
     // 2. unions between runs of neighbouring cube rows: thread = (row, direction group)
-    if (CC_CCL_LIST && list) {
+    if (list) {
         const int row = tid % NCROW, grp = tid / NCROW;          // grp is uniform per 2 waves
         const int cz = row / CY, cy = row % CY;
         const int dz = grp == 3 ? 0 : -1, dy = grp == 3 ? -1 : grp - 1;
@@ -205,7 +197,6 @@ __device__ __forceinline__ u32 tile_ccl(const u64* rows, TileCCL& T, u32* list =
                 ++pos;
             }
         __syncthreads();
-        if (STOP == 4) return 0;       // ablation: the pair list without the unions
         const u32 nl = total < (u32)NRUN ? total : (u32)NRUN;
         for (u32 i = tid; i < nl; i += NTHREADS) {
             const u32 e = list[i];
@@ -248,7 +239,6 @@ __device__ __forceinline__ u32 tile_ccl(const u64* rows, TileCCL& T, u32* list =
         }
     }
     __syncthreads();
-    if (STOP == 2) return 0;
     // 3. compress; count the roots of each quarter row.  The finds here must not compress
     // paths: a compressing find of another thread could store an intermediate ancestor into
     // par[r] after r's owner stored the root, and phase 5 would then read that ancestor's entry
@@ -264,7 +254,6 @@ __device__ __forceinline__ u32 tile_ccl(const u64* rows, TileCCL& T, u32* list =
         n += (root == r);
     }
     __syncthreads();
-    if (STOP == 3) return 0;
     // 4. compact index k of every root, in run-id order; a root also records its cube layer cz in
     // bits 12-14 (run ids < 4096): the component's first voxel lies in that layer (the root is
     // its first run in cube order, so no run of it has a smaller cz), so phase 5 only offers
@@ -515,7 +504,8 @@ __device__ __forceinline__ u32 face_word(int w, const u64* rows, const TileCCL& 
 }
 
 // ------------------------------------------------------------------------------------------
-// k_pass1: bit rows, tile-local components, their first voxels, face planes
+// Pass 1 of a tile (inside k_spec / k_fix): bit rows, tile-local components, their first voxels,
+// face planes
 // ------------------------------------------------------------------------------------------
 // LDS of one pass-1 tile
 struct Pass1LDS {
@@ -524,47 +514,19 @@ struct Pass1LDS {
     u32 key[NRUN];            // first voxel (tile raster index) of each component (<= one per run)
 };
 
-template <int ABL>
-__device__ __forceinline__ void pass1_finish(const Geom& g, int64_t t, const TileInfo& ti, u64* BITS, face_t* FACES,
-                                             u32* COUNT, u32* P, u64* KEY, Pass1LDS& L, bool write,
-                                             u8* fchg = nullptr, int empty = -1);
-
-// Pass 1 of tile t (block parameters p): bit rows -> BITS, tile CCL -> COUNT, nodes (P, KEY),
-// face planes.  ABL (kernel ablation harness tools/ablate.hip only; 0 in the library): stop
-// after phase ABL (1 bits, 2 CCL, 3 first voxels; 11..13 inside the CCL after its phase 1..3).
-template <bool HAS_MASK, int ABL = 0>
-__device__ __forceinline__ void pass1_tile(const Geom& g, int64_t t, const TileInfo& ti, const BlockParam& p,
-                                           const float* __restrict__ in, const u8* __restrict__ mask, float thr,
-                                           int mode, u64* BITS, face_t* FACES, u32* COUNT, u32* P, u64* KEY,
-                                           Pass1LDS& L, bool write = true, u8* fchg = nullptr) {
-    const int tid = cc_tid();
-    for (int i = tid; i < NROWS; i += NTHREADS) L.rows[i] = 0;
-    __syncthreads();
-    if (p.kind != BP_EMPTY) load_rows<HAS_MASK>(g, ti, in, mask, p, thr, mode, L.rows);
-    __syncthreads();
-    pass1_finish<ABL>(g, t, ti, BITS, FACES, COUNT, P, KEY, L, write, fchg);
-}
-
-// pass 1's BITS / FACES stores, non-temporal (CC_SPEC_NT=0 for A/B: plain stores; C3 on a fast box
-// k_spec 3.140-3.148 -> 3.113-3.122 ms, C4 unchanged: profiles/r05_ab_spec_nt.txt)
-#ifndef CC_SPEC_NT
-#define CC_SPEC_NT 1
-#endif
+// pass 1's BITS / FACES stores, non-temporal (against plain stores, C3 on a fast box: k_spec
+// 3.140-3.148 -> 3.113-3.122 ms, C4 unchanged: profiles/r05_ab_spec_nt.txt)
 template <class T>
-__device__ __forceinline__ void spec_store(T* p, T v) {
-    if (CC_SPEC_NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+__device__ __forceinline__ void spec_store(T* p, T v) { __builtin_nontemporal_store(v, p); }
 
 // Pass 1 after the bit rows are in L.rows (and a barrier): BITS, tile CCL, COUNT, nodes, faces.
 // fchg (k_fix): fchg[t] = 1 when the new face planes differ from the ones in FACES (the seams
 // that read them must be redone; unchanged faces leave every seam list as it was).
 // empty: whether the tile has no foreground voxel, if the caller knows (k_spec reads it off its
 // statistics barrier); -1: decided here (one more barrier)
-template <int ABL>
 __device__ __forceinline__ void pass1_finish(const Geom& g, int64_t t, const TileInfo& ti, u64* BITS, face_t* FACES,
-                                             u32* COUNT, u32* P, u64* KEY, Pass1LDS& L, bool write, u8* fchg,
-                                             int empty) {
+                                             u32* COUNT, u32* P, u64* KEY, Pass1LDS& L, bool write,
+                                             u8* fchg = nullptr, int empty = -1) {
     u64* rows = L.rows;
     TileCCL& T = L.T;
     u32* key = L.key;
@@ -573,7 +535,7 @@ __device__ __forceinline__ void pass1_finish(const Geom& g, int64_t t, const Til
     // rows -- k_pass2 writes its zeros without them -- and skips the tile CCL; its faces are
     // stored as zeros (their readers take them as they are).
     static_assert(NROWS == NTHREADS, "one bit row per thread");
-    if (ABL == 0 && write && (empty >= 0 ? empty != 0 : !__syncthreads_or(rows[tid] != 0))) {
+    if (write && (empty >= 0 ? empty != 0 : !__syncthreads_or(rows[tid] != 0))) {
         if (tid == 0) COUNT[t] = 0;
         u32* FW = (u32*)(FACES + t * FACE_STRIDE);
         const bool two = NTHREADS + tid < FACE_STRIDE / 2;
@@ -585,16 +547,11 @@ __device__ __forceinline__ void pass1_finish(const Geom& g, int64_t t, const Til
         if (two) FW[NTHREADS + tid] = 0u;
         return;
     }
-    // (ABL 20 / 21 / 22: the whole pass without the BITS / FACES / both stores -- the store-volume
-    // ablation of tools/ablate.hip)
-    if (write && ABL != 20 && ABL != 22)
+    if (write)
         for (int i = tid; i < NROWS; i += NTHREADS) spec_store(BITS + t * NROWS + i, rows[i]);
-    if (ABL == 1) return;
-    if constexpr (ABL >= 10 && ABL < 20) { tile_ccl<ABL - 10>(rows, T, key, key); return; }
     const u32 R = tile_ccl(rows, T, key, key);      // key[k] = first voxel of component k
-    if (ABL == 2) { if (tid == 0) COUNT[t] = R; return; }
     if (tid == 0 && write) COUNT[t] = R;
-    if (ABL == 3 || !write) return;
+    if (!write) return;
     const u32 base = (u32)(t * g.cap);
     for (u32 k = tid; k < R; k += NTHREADS) {
         const u32 node = base + k;
@@ -612,33 +569,23 @@ __device__ __forceinline__ void pass1_finish(const Geom& g, int64_t t, const Til
         const bool diff = FW[tid] != w0 || (two && FW[NTHREADS + tid] != w1);
         if (__syncthreads_or(diff) && tid == 0) fchg[t] = 1;
     }
-    if (ABL == 21 || ABL == 22) {          // ablation: faces computed, not stored
-        if (__syncthreads_or(w0 == 0x12345678u && w1 == 0x9ABCDEF0u) && tid == 0) COUNT[t] = R + 1;
-        return;
-    }
     spec_store(FW + tid, w0);
     if (two) spec_store(FW + NTHREADS + tid, w1);
 }
 
-// k_pass1: one workgroup per tile, block parameters precomputed (ablation harness; the library
-// runs pass 1 inside k_spec / k_fix)
-template <bool HAS_MASK, int ABL = 0>
-__global__ __launch_bounds__(NTHREADS) void k_pass1(Geom g, const float* __restrict__ in,
-                                                    const u8* __restrict__ mask, const BlockParam* bp,
-                                                    float thr, int mode, u64* BITS, face_t* FACES,
-                                                    u32* COUNT, u32* P, u64* KEY) {
-    __shared__ Pass1LDS L;
-    const int64_t t = blockIdx.x;
-    const TileInfo ti = tile_info(g, t);
-    pass1_tile<HAS_MASK, ABL>(g, t, ti, uniform_bp(bp[ti.block]), in, mask, thr, mode, BITS, FACES, COUNT, P, KEY, L);
-}
-
-// global tile id of local tile lt (z-major inside the block) of block b
-__device__ __forceinline__ int64_t block_tile(const Geom& g, int64_t b, int lt) {
-    const int bx = (int)(b % g.nb[2]), by = (int)((b / g.nb[2]) % g.nb[1]), bz = (int)(b / ((int64_t)g.nb[2] * g.nb[1]));
-    const int nx = g.btn[2][bx], ny = g.btn[1][by];
-    const int lx = lt % nx, ly = (lt / nx) % ny, lz = lt / (nx * ny);
-    return ((int64_t)(g.bt0[0][bz] + lz) * g.nt[1] + (g.bt0[1][by] + ly)) * g.nt[2] + (g.bt0[2][bx] + lx);
+// Pass 1 of tile t (block parameters p): bit rows -> BITS, tile CCL -> COUNT, nodes (P, KEY),
+// face planes.
+template <bool HAS_MASK>
+__device__ __forceinline__ void pass1_tile(const Geom& g, int64_t t, const TileInfo& ti, const BlockParam& p,
+                                           const float* __restrict__ in, const u8* __restrict__ mask, float thr,
+                                           int mode, u64* BITS, face_t* FACES, u32* COUNT, u32* P, u64* KEY,
+                                           Pass1LDS& L, bool write = true, u8* fchg = nullptr) {
+    const int tid = cc_tid();
+    for (int i = tid; i < NROWS; i += NTHREADS) L.rows[i] = 0;
+    __syncthreads();
+    if (p.kind != BP_EMPTY) load_rows<HAS_MASK>(g, ti, in, mask, p, thr, mode, L.rows);
+    __syncthreads();
+    pass1_finish(g, t, ti, BITS, FACES, COUNT, P, KEY, L, write, fchg);
 }
 
 // tile tables read after stores come back in VGPRs (vector loads); the values are
@@ -664,8 +611,8 @@ __device__ __forceinline__ TileInfo uniform_ti(TileInfo ti) {
 // interval [lg, hg], and records per tile the nearest values on both sides of each guessed bound:
 //   TB = { max ord < lg, min ord >= lg, max ord <= hg, min ord > hg }  (masked-out voxels excluded).
 // With the exact interval [lt, ht] (k_block_params) a tile's bits are the exact bits iff no voxel
-// lies between lg and lt nor between hg and ht -- decided from TB alone (spec_valid).  k_verify
-// k_verify lists the tiles that fail and k_fix relabels them from the input with the exact interval.
+// lies between lg and lt nor between hg and ht -- decided from TB alone (spec_valid).
+// k_params_verify lists the tiles that fail and k_fix relabels them from the input with the exact interval.
 // A one-sided interval is kept open to the end of the order (widen): it then differs from the
 // exact one only in its finite bound.  On quantized data the sampled extremes are usually the
 // block's and the guess is exact; on continuous data it misses the exact bound by about the
@@ -710,57 +657,16 @@ __device__ __forceinline__ u32 block_minmax(u32 v, u32* red) {
     return v;
 }
 
-// k_spec's float4 input loads, non-temporal (the input is read once): C3 k_spec 3.09-3.11 ->
-// 2.98-3.00 ms, C4 4.06 -> 3.97 ms on a fast-kind box (profiles/r05_ab_ntload.txt; CC_SPEC_NTLOAD=0
-// for A/B)
-#ifndef CC_SPEC_NTLOAD
-#define CC_SPEC_NTLOAD 1
-#endif
+// The float4 input loads of k_spec and k_sample, non-temporal (the input is read once).  Measured
+// on a fast-kind box (profiles/r05_ab_ntload.txt): C3 k_spec 3.09-3.11 -> 2.98-3.00 ms, C4 4.06 ->
+// 3.97 ms; C3 k_sample 0.114 -> 0.055 ms.  The other read-once streams measured worse or equal
+// that way and stay plain loads -- k_spec's mask 4.40 -> 4.89 ms at C4, k_seams' face planes
+// 0.272 -> 0.285 ms, k_pass2's bit rows equal -- and so do k_pass2's label stores (non-temporal:
+// 5.52 -> 5.80 ms), same file.
 __device__ __forceinline__ float4 ld_in4(const float* p) {
-#if CC_SPEC_NTLOAD
     typedef float v4f __attribute__((ext_vector_type(4)));
     const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
     return float4{v.x, v.y, v.z, v.w};
-#else
-    return *reinterpret_cast<const float4*>(p);
-#endif
-}
-
-// k_sample's rows, non-temporal too (C3 k_sample 0.114 -> 0.055 ms; CC_SAMPLE_NT=0 for A/B).  The
-// other read-once streams measured worse or equal that way (CC_RD_NT, A/B only: k_spec's mask
-// 4.40 -> 4.89 ms at C4, k_seams' face planes 0.272 -> 0.285 ms, k_pass2's bit rows equal), and so
-// did k_pass2's label stores (CC_P2_NTSTORE: 5.52 -> 5.80 ms): profiles/r05_ab_ntload.txt
-#ifndef CC_SAMPLE_NT
-#define CC_SAMPLE_NT 1
-#endif
-#ifndef CC_RD_NT
-#define CC_RD_NT 0
-#endif
-#ifndef CC_P2_NTSTORE
-#define CC_P2_NTSTORE 0
-#endif
-template <class T>
-__device__ __forceinline__ T ld_once(const T* p) {
-    if constexpr (CC_RD_NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-__device__ __forceinline__ float4 ld_sample4(const float* p) {
-#if CC_SAMPLE_NT
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-    return float4{v.x, v.y, v.z, v.w};
-#else
-    return *reinterpret_cast<const float4*>(p);
-#endif
-}
-__device__ __forceinline__ uint4 ld_once_u4(const void* p) {
-#if CC_RD_NT
-    typedef u32 v4u __attribute__((ext_vector_type(4)));
-    const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p));
-    return uint4{v.x, v.y, v.z, v.w};
-#else
-    return *reinterpret_cast<const uint4*>(p);
-#endif
 }
 
 // k_sample: workgroup (b, part) reads every SAMPLE_PARTS-th sample row of block b and writes its
@@ -854,7 +760,7 @@ __global__ __launch_bounds__(NTHREADS) void k_sample(Geom g, const float* __rest
                     const int j = min(j0 + 4 * u + slot, nj - 1);             // repeats are harmless
                     const int r = pt + SAMPLE_PARTS * j;
                     const int z = e0[0] + (r / nys) * SAMPLE_DZ + zo, y = e0[1] + (r % nys) * SAMPLE_DY + yo;
-                    v[u] = ld_sample4(in + ((int64_t)z * g.Y + y) * g.X + e0[2] + x);
+                    v[u] = ld_in4(in + ((int64_t)z * g.Y + y) * g.X + e0[2] + x);
                 }
 #pragma unroll
                 for (int u = 0; u < SAMPLE_U; ++u) {
@@ -973,14 +879,10 @@ __device__ __forceinline__ int64_t xcd_contig(int64_t b, int64_t n) {
     return k * q + (k < r ? k : r) + i;
 }
 
-// mask bytes: 4 per lane and plane (default), or 16 per lane staged through LDS (CC_MASK_STAGE=1,
-// A/B only).  With plain input loads the staging won on the slow box kind (C4 k_spec<true>
-// 4.90-4.95 -> 4.72-4.76 ms) and lost on the fast one (profiles/r05_ab_mstage*.txt); with the
-// non-temporal input loads the 4-B loads win (fast kind 4.04-4.07 -> 3.96-3.97 ms:
-// profiles/r05_ab_c4_order_mask.txt)
-#ifndef CC_MASK_STAGE
-#define CC_MASK_STAGE 0
-#endif
+// mask bytes: 4 per lane and plane.  16 per lane staged through LDS was tried: with plain input
+// loads the staging won on the slow box kind (C4 k_spec<true> 4.90-4.95 -> 4.72-4.76 ms) and lost
+// on the fast one (profiles/r05_ab_mstage*.txt); with the non-temporal input loads the 4-B loads
+// win (fast kind 4.04-4.07 -> 3.96-3.97 ms: profiles/r05_ab_c4_order_mask.txt)
 
 // The front of k_spec for tile t: the tile's voxels in one read -> exact statistics (the
 // block's atomics), the bit rows under the guessed interval [lo, hi] into L.rows, the tile's TB
@@ -1047,18 +949,7 @@ __device__ __forceinline__ bool spec_front(const Geom& g, const SpecArgs& sa, in
         const int i4 = 4 * (lane & 15);
         const int64_t sz = g.Y * g.X;
         const float* pz = in + ((int64_t)ti.z0 * g.Y + ti.y0 + 4 * wave + (lane >> 4)) * g.X + ti.x0 + i4;
-#if !CC_MASK_STAGE
         const u8* mz = HAS_MASK ? mask + (pz - in) : nullptr;
-#else
-        // mask bytes 16 per lane: per group of 4 planes lane L loads 16 B of
-        // plane z0 + L / 16, row 4w + (L / 4) % 4, x = 16 (L % 4) and stages them in the wave's
-        // 1 KB of LDS (L.key, unused until the tile CCL), where lane m finds its 4 bytes of plane a
-        // at word a * 64 + m (one 16-B load instead of four 4-B loads per lane and group)
-        const u8* mz16 = HAS_MASK ? mask + ((int64_t)ti.z0 * g.Y + ti.y0 + 4 * wave + ((lane >> 2) & 3)) * g.X + ti.x0 +
-                                        16 * (lane & 3) + (int64_t)(lane >> 4) * sz
-                                  : nullptr;
-        u32* mstage = L.key + wave * 256;
-#endif
         constexpr int RZ4 = 4;
         u32 R[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // lane z: ballots (lo, hi) of values 0..3 of plane z
         auto plane_bits = [&](int z, float4 v, uchar4 mk) {
@@ -1073,18 +964,10 @@ __device__ __forceinline__ bool spec_front(const Geom& g, const SpecArgs& sa, in
         for (int z0 = 0; z0 < TZ; z0 += RZ4) {
             float4 v[RZ4];
             uchar4 mk[RZ4];
-#if CC_MASK_STAGE
-            if (HAS_MASK) reinterpret_cast<uint4*>(mstage)[lane] = ld_once_u4(mz16 + z0 * sz);
-            auto ld = [&](int a) {
-                v[a] = ld_in4(pz + (z0 + a) * sz);
-                if (HAS_MASK) mk[a] = __builtin_bit_cast(uchar4, mstage[a * 64 + lane]);
-            };
-#else
             auto ld = [&](int a) {
                 v[a] = ld_in4(pz + (z0 + a) * sz);
                 if (HAS_MASK) mk[a] = *reinterpret_cast<const uchar4*>(mz + (z0 + a) * sz);
             };
-#endif
 #pragma unroll
             for (int a = 0; a < RZ4; ++a) {
                 // each load issued right before its use, one in flight per wave (an empty asm
@@ -1173,9 +1056,7 @@ __device__ __forceinline__ bool spec_front(const Geom& g, const SpecArgs& sa, in
 #endif
 
 // SIDES: bounds of the guessed interval that can move (1 lower: 'greater', 2 upper: 'less', 3 both)
-// ABL (kernel ablation harness tools/ablate.hip only; 0 in the library): 99 stop once the bit rows
-// are in LDS (loads, ballots, statistics), else as pass1_finish's ABL
-template <bool HAS_MASK, int SIDES, int ABL = 0>
+template <bool HAS_MASK, int SIDES>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_spec(
     Geom g, SpecArgs sa, const float* __restrict__ in, const u8* __restrict__ mask, u64* BITS, face_t* FACES,
     u32* COUNT, u32* P, u64* KEY) {
@@ -1186,7 +1067,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(8, 8))
     const TileInfo ti = tile_info(g, t);
     if (HAS_MASK && sa.live && !__builtin_amdgcn_readfirstlane(sa.live[ti.block])) {
         // a block without a mask voxel: nothing is read, the tile is empty (COUNT 0, zero faces)
-        pass1_finish<ABL % 99>(g, t, ti, BITS, FACES, COUNT, P, KEY, L, true, nullptr, 1);
+        pass1_finish(g, t, ti, BITS, FACES, COUNT, P, KEY, L, true, nullptr, 1);
         return;
     }
     const BlockParam p = uniform_bp(sa.guess[ti.block]);
@@ -1195,8 +1076,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(8, 8))
         return;
     }
     const bool empty = spec_front<HAS_MASK, SIDES>(g, sa, t, ti, in, mask, p.lo, p.hi, L, red);
-    if (ABL == 99) return;
-    pass1_finish<ABL % 99>(g, t, ti, BITS, FACES, COUNT, P, KEY, L, true, nullptr, empty ? 1 : 0);
+    pass1_finish(g, t, ti, BITS, FACES, COUNT, P, KEY, L, true, nullptr, empty ? 1 : 0);
     CC_KERNEL_PROBE_END
 }
 
@@ -1209,16 +1089,9 @@ __device__ __forceinline__ bool spec_valid(const BlockParam& G, BlockParam T, co
     return true;
 }
 
-// FIX[0] = number of tiles to relabel, FIX[1..] = their ids
-__global__ void k_verify(Geom g, const BlockParam* guess, const BlockParam* bp, const u32* TB, int mode, u32* FIX) {
-    CC_FOR(t, g.n_tiles) {
-        const int64_t b = tile_info(g, t).block;
-        if (!spec_valid(guess[b], bp[b], TB + 4 * t, mode)) FIX[1 + atomicAdd(FIX, 1u)] = (u32)t;
-    }
-}
-
-// k_block_params and k_verify in one launch: every tile derives its block's exact parameters from
-// the statistics (a few dozen float ops), the block's first tile stores them for k_fix
+// k_block_params and the verification in one launch: every tile derives its block's exact
+// parameters from the statistics (a few dozen float ops), the block's first tile stores them for
+// k_fix; FIX[0] = number of tiles to relabel, FIX[1..] = their ids
 // live (nullable, masked runs): a block without a mask voxel gets no foreground (BP_EMPTY) and
 // none of its tiles is listed (k_spec left them empty without reading them)
 __global__ void k_params_verify(Geom g, const BlockParam* guess, const u32* smin, const u32* smax, const u32* sflag,
@@ -1320,7 +1193,7 @@ __device__ __forceinline__ void stage_faces(const Geom& g, const face_t* __restr
         for (int j = 0; j < NJ; ++j) {
             const int w = tid + 64 * j;
             const int64_t ts = src(128 * j);
-            v[j] = (w < FACE_STRIDE / 2 && ts >= 0) ? ld_once(FW + ts * (FACE_STRIDE / 2) + w) : 0u;
+            v[j] = (w < FACE_STRIDE / 2 && ts >= 0) ? FW[ts * (FACE_STRIDE / 2) + w] : 0u;
         }
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -1571,14 +1444,6 @@ constexpr int TPC = 512;           // pair slots per tile
 constexpr int SB_THREADS = 1024;
 constexpr int SB_MAXT = 1024;
 constexpr int SB_LCAP = 8192;
-
-// index of tile t inside its block (z-major over the block's tiles); tile ids fit u32
-__device__ __forceinline__ u32 block_local(const Geom& g, u32 t) {
-    const u32 n2 = (u32)g.nt[2], n1 = (u32)g.nt[1];
-    const u32 q = t / n2, ix = t - q * n2, iz = q / n1, iy = q - iz * n1;
-    const int bz = g.tblk[0][iz], by = g.tblk[1][iy], bx = g.tblk[2][ix];
-    return (u32)(((iz - g.bt0[0][bz]) * g.btn[1][by] + (iy - g.bt0[1][by])) * g.btn[2][bx] + (ix - g.bt0[2][bx]));
-}
 
 // Wave-level duplicate filter: lanes whose key equals the first active lane's key drop out (two
 // rounds); returns whether this lane still has to emit its key.
@@ -1861,7 +1726,6 @@ __device__ __forceinline__ void seam_edges_rows(const face_t* S, const face_t* E
     }
 }
 
-// STOP (ablation harness only; 0 in the library): 1 staged, 2 + z seam, 3 + y seam, 4 + x seam
 // Tiles [t_begin, t_end): the seams of a z-layer chunk only read faces of that chunk and the
 // layers below it, so the library runs them on a side stream behind the k_spec chunks.
 // list (nullable): the tiles are list[1 .. list[0]] instead of the range (seams redone after k_fix)
@@ -1873,7 +1737,6 @@ struct SeamsLDS {
 };
 
 // the seams of tile t (valid) for wave w; every wave of the workgroup calls it (one barrier)
-template <int STOP = 0>
 __device__ __forceinline__ void seams_tile(const Geom& g, const face_t* __restrict__ FACES, const u32* __restrict__ COUNT,
                                            u64* PAIRS, u32* PC, u8* big, u64* IPAIRS, u32* IPC, u8* iovf, int64_t t,
                                            bool valid, SeamsLDS& LS) {
@@ -1952,7 +1815,6 @@ __device__ __forceinline__ void seams_tile(const Geom& g, const face_t* __restri
             append(to_inter, v);
         }
     };
-    if (STOP == 1) return;
     // first sighting of (neighbour, ka, kb) in this tile? (LDS hash set; a full set lets
     // duplicates through, which the consumers tolerate).  code: the neighbour's direction,
     // dz * 9 + (dy + 1) * 3 + (dx + 1) for the neighbour t - dz sz + dy sy + dx (distinct
@@ -1981,15 +1843,13 @@ __device__ __forceinline__ void seams_tile(const Geom& g, const face_t* __restri
         if (md_l == 1) push(false, ((u64)((lt_own << 12) | ka) << 32) | ((ltn_l << 12) | kb));
         else push(true, ((u64)((u32)t * capu + ka) << 32) | ((u32)tn_l * capu + kb));
     });
-    if (STOP != 4) {
-        // edges and corners inside the block
-        seam_edges_rows(S, E, ti, nb, lane, [&](int oz, int oy, int ox, u32 k1, u32 k2) {
-            const u32 code = (u32)(-oz * 9 + (oy + 1) * 3 + (ox + 1));
-            if (!fresh(code, k1, k2)) return;
-            const u32 lt_e = lt_own + (u32)(oz * (int)bnyx + oy * (int)bnx + ox);
-            push(false, ((u64)((lt_own << 12) | k1) << 32) | ((lt_e << 12) | k2));
-        });
-    }
+    // edges and corners inside the block
+    seam_edges_rows(S, E, ti, nb, lane, [&](int oz, int oy, int ox, u32 k1, u32 k2) {
+        const u32 code = (u32)(-oz * 9 + (oy + 1) * 3 + (ox + 1));
+        if (!fresh(code, k1, k2)) return;
+        const u32 lt_e = lt_own + (u32)(oz * (int)bnyx + oy * (int)bnx + ox);
+        push(false, ((u64)((lt_own << 12) | k1) << 32) | ((lt_e << 12) | k2));
+    });
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     // the stashes: slot-major, lane order inside a slot, behind the overflow appends
@@ -2021,7 +1881,6 @@ __device__ __forceinline__ void seams_tile(const Geom& g, const face_t* __restri
     }
 }
 
-template <int STOP = 0>
 __global__ __launch_bounds__(SP_WAVES * 64) void k_seams(Geom g, const face_t* __restrict__ FACES,
                                                          const u32* __restrict__ COUNT, u64* PAIRS, u32* PC,
                                                          u8* big, u64* IPAIRS, u32* IPC, u8* iovf,
@@ -2036,7 +1895,7 @@ __global__ __launch_bounds__(SP_WAVES * 64) void k_seams(Geom g, const face_t* _
         valid = idx < (int64_t)nl;
         t = valid ? (int64_t)__builtin_amdgcn_readfirstlane(list[1 + idx]) : 0;
     }
-    seams_tile<STOP>(g, FACES, COUNT, PAIRS, PC, big, IPAIRS, IPC, iovf, t, valid, LS);
+    seams_tile(g, FACES, COUNT, PAIRS, PC, big, IPAIRS, IPC, iovf, t, valid, LS);
 }
 
 // the listed tiles list[1 .. list[0]] with a fixed grid (the count stays on the device: the
@@ -2053,7 +1912,7 @@ __global__ __launch_bounds__(SP_WAVES * 64) void k_seams_list(Geom g, const face
         const int64_t idx = i0 + w;
         const bool valid = idx < (int64_t)nl;
         const int64_t t = valid ? (int64_t)__builtin_amdgcn_readfirstlane(list[1 + idx]) : 0;
-        seams_tile<0>(g, FACES, COUNT, PAIRS, PC, big, IPAIRS, IPC, iovf, t, valid, LS);
+        seams_tile(g, FACES, COUNT, PAIRS, PC, big, IPAIRS, IPC, iovf, t, valid, LS);
         __syncthreads();
     }
 }
@@ -2621,14 +2480,7 @@ __device__ __forceinline__ void write_status(const StatusArgs& sa, const u64* sc
     }
 }
 
-// lut[i] = base + i for the ids of this volume (slab): i in [0, scalars[0]] (the last one is
-// the slack id n_labels - 1 on the last slab, merge_offsets.py:120)
-__global__ void k_lut_init(u64 cap, const u64* scalars, u64 base, u64* lut) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap && i <= scalars[0]) lut[i] = base + i;
-}
-
-// k_lut_init and k_lut in one launch: the LUT entry of every id of this volume (slab) -- a root's
+// k_lut_all: the LUT entry of every id of this volume (slab), one launch -- a root's
 // id maps to its component's representative, every other id (label 0 of a block, the slack id) to
 // itself; lut holds cap >= scalars[0] + 1 entries.  sums (nullable; the one-read-back shard schedule): offsets and KR are
 // this slab's own id space (base 0) and the global base = sum of sums[0 .. rank) is added here;
@@ -2680,17 +2532,6 @@ __global__ __launch_bounds__(256) void k_status(StatusArgs st, const u64* scalar
     if (sums)
         for (int r = 0; r < rank; ++r) gbase += sums[r];
     write_status(st, scalars, sums, gbase);
-}
-
-__global__ void k_lut(int64_t n, const u32* vals, u32* P, const u64* KR, u64 base, const u64* U, const u64* V,
-                      int64_t m, u64* lut, u64* scalars) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const u32 node = vals[i];
-    const u32 r = gfind(P, node);
-    const u64 rep = apply_map(KR[r], U, V, m);
-    lut[KR[node] - base] = rep;
-    if (r == node && rep == KR[r]) atomicAdd((unsigned long long*)&scalars[1], 1ull);   // components owned here
 }
 
 // final label of every node into FIN (a separate buffer).  LOCAL (stage-level block_components)
@@ -3102,12 +2943,7 @@ constexpr int LABCAP = 2048;          // component labels cached in LDS
 // 5.50 ms at C3, same box)
 __device__ __forceinline__ void store2(u64* __restrict__ out, int64_t idx, u64 v0, u64 v1, bool two, bool vec) {
     if (two && vec) {
-#if CC_P2_NTSTORE
-        typedef u64 v2u __attribute__((ext_vector_type(2)));
-        __builtin_nontemporal_store(v2u{v0, v1}, reinterpret_cast<v2u*>(out + idx));
-#else
         *reinterpret_cast<ulonglong2*>(out + idx) = make_ulonglong2(v0, v1);
-#endif
     } else {
         out[idx] = v0;
         if (two) out[idx + 1] = v1;
@@ -3184,7 +3020,7 @@ __global__ __launch_bounds__(NTHREADS) void k_pass2(Geom g, const u64* __restric
         const u32 k = tid + j * NTHREADS;
         lv[j] = k < R ? label(base + k) : 0ull;
     }
-    for (int i = tid; i < NROWS; i += NTHREADS) rows[i] = ld_once(BITS + t * NROWS + i);
+    for (int i = tid; i < NROWS; i += NTHREADS) rows[i] = BITS[t * NROWS + i];
     __syncthreads();
     tile_ccl(rows, T, (u32*)lab);
 #pragma unroll
@@ -3458,7 +3294,6 @@ __global__ __launch_bounds__(NTHREADS) void k_thr_fix(Geom g, const u32* FIX, co
     template __global__ void k_spec<M, S>(Geom, SpecArgs, const float*, const u8*, u64*, face_t*, u32*, u32*, u64*);
 CC_SPEC(false, 1) CC_SPEC(false, 2) CC_SPEC(false, 3) CC_SPEC(true, 1) CC_SPEC(true, 2) CC_SPEC(true, 3)
 #undef CC_SPEC
-template __global__ void k_seams<0>(Geom, const face_t*, const u32*, u64*, u32*, u8*, u64*, u32*, u8*, int64_t, int64_t, const u32*);
 template __global__ void k_stitch<false>(Geom, const face_t*, u32*, const u64*, const u8*, const u8*);
 template __global__ void k_stitch<true>(Geom, const face_t*, u32*, const u64*, const u8*, const u8*);
 template __global__ void k_finalize<true>(Geom, const u32*, u32*, const u64*, const u64*, const u64*, const u64*, int64_t, u64*);

@@ -124,7 +124,7 @@ static void phase_local(cc_ctx* c, const float* in, const uint8_t* mask, const i
         sa.live = live;
         auto seams = [&](hipStream_t q, int64_t t0, int64_t t1) {
             launch_on(c, q, "k_seams", [&] {
-                k_seams<0><<<(unsigned)((t1 - t0 + SP_WAVES - 1) / SP_WAVES), SP_WAVES * 64, 0, q>>>(
+                k_seams<<<(unsigned)((t1 - t0 + SP_WAVES - 1) / SP_WAVES), SP_WAVES * 64, 0, q>>>(
                     g, FACES, COUNT, c->pairsl.as<u64>(), c->pc.as<u32>(), c->big.as<u8>(), c->ipairs.as<u64>(),
                     c->ipc.as<u32>(), c->iovf.as<u8>(), t0, t1, nullptr);
             });
@@ -146,8 +146,7 @@ static void phase_local(cc_ctx* c, const float* in, const uint8_t* mask, const i
             sa.t0 = t0;
             const unsigned ng = (unsigned)(t1 - t0);
             launch(c, "k_spec", [&] {
-#define CC_SPEC_LAUNCH(M, S) k_spec<M, S><<<ng, NTHREADS, spad, s>>>(g, sa, in, mask, BITS, FACES, COUNT, P, KR)
-                const unsigned spad = (unsigned)env_int("CC_LDS_PAD_SPEC", 0);   // A/B only, as CC_LDS_PAD_P2
+#define CC_SPEC_LAUNCH(M, S) k_spec<M, S><<<ng, NTHREADS, 0, s>>>(g, sa, in, mask, BITS, FACES, COUNT, P, KR)
                 if (mask) {
                     if (mode == MODE_GREATER) CC_SPEC_LAUNCH(true, 1);
                     else if (mode == MODE_LESS) CC_SPEC_LAUNCH(true, 2);
@@ -212,7 +211,7 @@ static void phase_local(cc_ctx* c, const float* in, const uint8_t* mask, const i
                 // work to the global fallback, which reads the current faces)
                 const int64_t nl = std::min<int64_t>(nt, 14 * (int64_t)nfix);
                 launch(c, "k_seams", [&] {
-                    k_seams<0><<<(unsigned)((nl + SP_WAVES - 1) / SP_WAVES), SP_WAVES * 64, 0, s>>>(
+                    k_seams<<<(unsigned)((nl + SP_WAVES - 1) / SP_WAVES), SP_WAVES * 64, 0, s>>>(
                         g, FACES, COUNT, c->pairsl.as<u64>(), c->pc.as<u32>(), c->big.as<u8>(), c->ipairs.as<u64>(),
                         c->ipc.as<u32>(), c->iovf.as<u8>(), 0, 0, list);
                 });
@@ -644,13 +643,11 @@ static void phase_final(cc_ctx* c, uint64_t* out, cc_result* res, const SeamDev*
         // profiles/r05_ab_c4_order_mask.txt; C3 unmasked is slower that way, 5.49-5.53 -> 5.70)
         int order = g.X >= 4096 ? 1 : ((g.X & 15) || st.masked) ? 2 : 0;
         if (const char* e = std::getenv("CC_PASS2_ORDER"); e && *e) order = std::min(std::max(std::atoi(e), 0), 5);
-        // CC_LDS_PAD_P2 (A/B only): extra dynamic LDS per workgroup, i.e. fewer tiles per CU
-        const unsigned pad = (unsigned)env_int("CC_LDS_PAD_P2", 0);
         // with a seam map every label goes through the slab's LUT (m = 1)
         const int64_t mm = sd ? 1 : m;
-        if (st.local_only) k_pass2<false><<<(unsigned)nt, NTHREADS, pad, s>>>(g, c->bits.as<u64>(), COUNT, FIN, nullptr, nullptr, 0, 0, out, order, nullptr, nullptr);
-        else k_pass2<true><<<(unsigned)nt, NTHREADS, pad, s>>>(g, c->bits.as<u64>(), COUNT, KR, P, c->lut.as<u64>(), st.base, mm, out, order,
-                                                               nullptr, sd ? scalars : nullptr, lut_cap);
+        if (st.local_only) k_pass2<false><<<(unsigned)nt, NTHREADS, 0, s>>>(g, c->bits.as<u64>(), COUNT, FIN, nullptr, nullptr, 0, 0, out, order, nullptr, nullptr);
+        else k_pass2<true><<<(unsigned)nt, NTHREADS, 0, s>>>(g, c->bits.as<u64>(), COUNT, KR, P, c->lut.as<u64>(), st.base, mm, out, order,
+                                                             nullptr, sd ? scalars : nullptr, lut_cap);
     });
 
     u64 sc[4] = {0, 0, 0, 0};

@@ -227,8 +227,7 @@ struct SfGeom {
 
 static SfGeom sf_geom(const void* a, const void* b, int64_t n) {
     SfGeom g;
-    // (CC_SF_VW = 1: A/B only, the one-id-per-lane path whatever the alignment)
-    g.vw2 = ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0) && env_int("CC_SF_VW", 2) != 1;
+    g.vw2 = ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0);
     const int64_t step = (int64_t)RL_WG * RL_Q * (g.vw2 ? 2 : 1), steps = (n + step - 1) / step;
     g.per_wg = ((steps + 8191) / 8192) * step;
     g.grid = (unsigned)((n + g.per_wg - 1) / g.per_wg);

@@ -6,8 +6,11 @@ output_path / output_key / threshold / threshold_mode / channel / dependency, th
 (sigma_prefilter, chunks, compression), the uint8 output dataset with chunks block_shape // 2
 clipped to the shape, the job config per LocalTask and the "processed job" log contract.  The
 job's compute (per-block normalize + float32 compare, threshold.py:131-171) runs on the MI355X
-through cc_threshold (k_block_stats -> k_block_params -> k_threshold); one GPU job thresholds
-the whole volume and writes the listed blocks.  channel (4-D input): the listed channels are
+through cc_threshold -- by default one read of the input: k_sample + k_guess -> k_thr_spec ->
+k_params_verify -> k_thr_fix (every block thresholded under a guessed interval, the tiles the
+guess was not exact for rewritten); with CC_THRESHOLD_TWO_PASS=1 the two-read path k_block_stats
+-> k_block_params -> k_threshold.  One GPU job thresholds the whole volume and writes the listed
+blocks.  channel (4-D input): the listed channels are
 averaged on the device first (cc_channel_mean, threshold.py:139-148); sigma_prefilter > 0: per block
 normalize + Gaussian smoothing first (cc_gaussian_smooth_blocks, threshold.py:150-153).
 """

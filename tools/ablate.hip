@@ -1,13 +1,15 @@
-// tools/ablate.hip -- kernel ablation / roofline harness (timing only, not part of the library).
+// tools/ablate.hip -- whole-kernel timing / roofline harness (timing only, not part of the library).
 //
-// Runs the volume-sized kernels of the path on a synthetic boundary map already in HBM and times
-// each variant with HIP events over `iters` launches:
+// Runs the volume-sized kernels of the path, as the library ships them, on a synthetic boundary
+// map already in HBM and times each with HIP events over `iters` launches:
 //   copy_read / copy_write   plain float4 streaming read / 16-B uint64 store (the box's HBM ceiling)
 //   k_block_stats            per-block min/max pass
-//   k_pass1 ABL=1,2,3,0      stop after: load+threshold+bits | + tile CCL | + first voxels | full
 //   k_sample_guess / k_spec  speculative front (guess = exact parameters: no relabelling)
-//   k_seams STOP variants    staged faces | + the three seams | full (edges, corners)
+//   k_spec_cached / k_block_stats_cached   the same with every tile reading one of 8 tiles in L2
+//   k_seams                  the tile seams (faces and counts of the k_spec run)
 //   k_pass2                  relabel + uint64 write (FIN = 0: timing only)
+// (The per-phase variants this harness used to time -- stops inside pass 1, the tile CCL and the
+// seams -- needed hooks in the kernels and left with them; DESIGN.md says which tree builds them.)
 // Build: make -C tools ablate   Run: tools/ablate Z Y X bz by bx [mode] [iters]
 #include <hip/hip_runtime.h>
 
@@ -114,18 +116,17 @@ int main(int argc, char** argv) {
         r.push_back({"copy_read", time_ms(s, iters, [&] { k_read<<<big, 256, 0, s>>>((const float4*)in, nvox / 4, dummy); })});
         r.push_back({"copy_write", time_ms(s, iters, [&] { k_write<<<big, 256, 0, s>>>((ulonglong2*)out, nvox / 2); })});
         r.push_back({"k_block_stats", time_ms(s, iters, stats)});
-#define P1(A) k_pass1<false, A><<<(unsigned)nt, NTHREADS, 0, s>>>(g, in, nullptr, bp, thr, mode, BITS, FACES, COUNT, P, KEY)
-        r.push_back({"k_pass1_abl1_load_bits", time_ms(s, iters, [&] { P1(1); })});
-        r.push_back({"k_pass1_ccl_ph1_runs", time_ms(s, iters, [&] { P1(11); })});
-        r.push_back({"k_pass1_ccl_ph2_unions", time_ms(s, iters, [&] { P1(12); })});
-        r.push_back({"k_pass1_ccl_ph3_compress", time_ms(s, iters, [&] { P1(13); })});
-        r.push_back({"k_pass1_abl2_ccl", time_ms(s, iters, [&] { P1(2); })});
-        r.push_back({"k_pass1_abl3_keys", time_ms(s, iters, [&] { P1(3); })});
-        r.push_back({"k_pass1_full", time_ms(s, iters, [&] { P1(0); })});
         // speculative front: sample + guess, k_spec with the exact parameters as the guess (no relabel)
+        u32 *fst, *TB;
+        BlockParam* guess;
+        SpecArgs sa;
+        auto spec = [&](const Geom& gs) {
+            if (mode == 0) k_spec<false, 1><<<(unsigned)nt, NTHREADS, 0, s>>>(gs, sa, in, nullptr, BITS, FACES, COUNT, P, KEY);
+            else if (mode == 1) k_spec<false, 2><<<(unsigned)nt, NTHREADS, 0, s>>>(gs, sa, in, nullptr, BITS, FACES, COUNT, P, KEY);
+            else k_spec<false, 3><<<(unsigned)nt, NTHREADS, 0, s>>>(gs, sa, in, nullptr, BITS, FACES, COUNT, P, KEY);
+        };
         {
-            u32 *fst, *part, *TB;
-            BlockParam* guess;
+            u32* part;
             HIP_OK(hipMalloc(&fst, 3 * nb * 4));
             HIP_OK(hipMalloc(&part, nb * SAMPLE_PARTS * 16));
             HIP_OK(hipMalloc(&TB, nt * 16));
@@ -139,24 +140,12 @@ int main(int argc, char** argv) {
             for (auto& q : hb)
                 if (q.kind == BP_INTERVAL) { if (mode == 0) q.hi = 0xFFFFFFFFu; else if (mode == 1) q.lo = 0; }
             HIP_OK(hipMemcpy(guess, hb.data(), nb * sizeof(BlockParam), hipMemcpyHostToDevice));
-            SpecArgs sa;
             sa.guess = guess; sa.smin = fst; sa.smax = fst + nb; sa.sflag = fst + 2 * nb; sa.TB = TB; sa.t0 = 0;
             r.push_back({"k_spec", time_ms(s, iters, [&] {
                 HIP_OK(hipMemsetAsync(fst, 0xFF, nb * 4, s));
                 HIP_OK(hipMemsetAsync(fst + nb, 0, 2 * nb * 4, s));
-                if (mode == 0) k_spec<false, 1><<<(unsigned)nt, NTHREADS, 0, s>>>(g, sa, in, nullptr, BITS, FACES, COUNT, P, KEY);
-                else if (mode == 1) k_spec<false, 2><<<(unsigned)nt, NTHREADS, 0, s>>>(g, sa, in, nullptr, BITS, FACES, COUNT, P, KEY);
-                else k_spec<false, 3><<<(unsigned)nt, NTHREADS, 0, s>>>(g, sa, in, nullptr, BITS, FACES, COUNT, P, KEY);
+                spec(g);
             })});
-#define SPS(A) k_spec<false, 1, A><<<(unsigned)nt, NTHREADS, 0, s>>>(g, sa, in, nullptr, BITS, FACES, COUNT, P, KEY)
-            r.push_back({"k_spec_nobits", time_ms(s, iters, [&] { SPS(20); })});
-            r.push_back({"k_spec_nofaces", time_ms(s, iters, [&] { SPS(21); })});
-            r.push_back({"k_spec_nostores", time_ms(s, iters, [&] { SPS(22); })});
-            r.push_back({"k_spec_rows", time_ms(s, iters, [&] { SPS(99); })});
-            r.push_back({"k_spec_bits", time_ms(s, iters, [&] { SPS(1); })});
-            r.push_back({"k_spec_ph2", time_ms(s, iters, [&] { SPS(12); })});
-            r.push_back({"k_spec_ccl", time_ms(s, iters, [&] { SPS(2); })});
-            r.push_back({"k_spec_keys", time_ms(s, iters, [&] { SPS(3); })});
         }
         // compute-bound variants: every tile reads one of 8 tiles that stay in L2 (tile origins
         // z = y = 0, x = 64 (ix % 8)); outputs per tile as usual
@@ -172,41 +161,15 @@ int main(int argc, char** argv) {
             HostGeom hc = hg;
             bind_geom_tables(hc, tabc);
             Geom gc = hc.g;
-            u32 *fst, *TB;
-            BlockParam* guess;
-            HIP_OK(hipMalloc(&fst, 3 * nb * 4));
-            HIP_OK(hipMalloc(&TB, nt * 16));
-            HIP_OK(hipMalloc(&guess, nb * sizeof(BlockParam)));
-            HIP_OK(hipMemcpy(guess, bp, nb * sizeof(BlockParam), hipMemcpyDeviceToDevice));
-            SpecArgs sa;
-            sa.guess = guess; sa.smin = fst; sa.smax = fst + nb; sa.sflag = fst + 2 * nb; sa.TB = TB; sa.t0 = 0;
-            r.push_back({"k_spec_cached", time_ms(s, iters, [&] {
-                k_spec<false, 1><<<(unsigned)nt, NTHREADS, 0, s>>>(gc, sa, in, nullptr, BITS, FACES, COUNT, P, KEY);
-            })});
-#define SPC(A) k_spec<false, 1, A><<<(unsigned)nt, NTHREADS, 0, s>>>(gc, sa, in, nullptr, BITS, FACES, COUNT, P, KEY)
-            r.push_back({"k_spec_rows_cached", time_ms(s, iters, [&] { SPC(99); })});
-            r.push_back({"k_spec_bits_cached", time_ms(s, iters, [&] { SPC(1); })});
-            r.push_back({"k_spec_ph1_cached", time_ms(s, iters, [&] { SPC(11); })});
-            r.push_back({"k_spec_ph2_cached", time_ms(s, iters, [&] { SPC(12); })});
-            r.push_back({"k_spec_ph3_cached", time_ms(s, iters, [&] { SPC(13); })});
-            r.push_back({"k_spec_ccl_cached", time_ms(s, iters, [&] { SPC(2); })});
-            r.push_back({"k_spec_keys_cached", time_ms(s, iters, [&] { SPC(3); })});
+            r.push_back({"k_spec_cached", time_ms(s, iters, [&] { spec(gc); })});
             r.push_back({"k_block_stats_cached", time_ms(s, iters, [&] {
                 k_block_stats<<<(unsigned)nt, NTHREADS, 0, s>>>(gc, in, smin, smax, sflag);
             })});
-#define P1C(A) k_pass1<false, A><<<(unsigned)nt, NTHREADS, 0, s>>>(gc, in, nullptr, bp, thr, mode, BITS, FACES, COUNT, P, KEY)
-            r.push_back({"k_pass1_abl1_cached", time_ms(s, iters, [&] { P1C(1); })});
-            r.push_back({"k_pass1_ph1_cached", time_ms(s, iters, [&] { P1C(11); })});
-            r.push_back({"k_pass1_ph2list_cached", time_ms(s, iters, [&] { P1C(14); })});
-            r.push_back({"k_pass1_ph2_cached", time_ms(s, iters, [&] { P1C(12); })});
-            r.push_back({"k_pass1_ph3_cached", time_ms(s, iters, [&] { P1C(13); })});
-            r.push_back({"k_pass1_abl2_cached", time_ms(s, iters, [&] { P1C(2); })});
-            r.push_back({"k_pass1_abl3_cached", time_ms(s, iters, [&] { P1C(3); })});
-            r.push_back({"k_pass1_full_cached", time_ms(s, iters, [&] { P1C(0); })});
         }
-        // seam kernel variants (FACES from the last full pass-1 run above)
+        // the seams of the faces and counts k_spec stores (run again on the real geometry: the
+        // cached variant above overwrote them)
         {
-            P1(0);
+            spec(g);
             u64 *pairs, *ipairs;
             u32 *pc, *ipc;
             u8 *big, *iovf;
@@ -214,17 +177,14 @@ int main(int argc, char** argv) {
             HIP_OK(hipMalloc(&ipairs, (size_t)nt * TPI * 8));
             HIP_OK(hipMalloc(&pc, nt * 4));
             HIP_OK(hipMalloc(&ipc, nt * 4));
-            HIP_OK(hipMalloc(&big, nb));
-            HIP_OK(hipMalloc(&iovf, nt));
-            HIP_OK(hipMemset(big, 0, nb));
-            HIP_OK(hipMemset(iovf, 0, nt));
+            HIP_OK(hipMalloc(&big, nb + 1));          // + the "any" flags big[nb] / iovf[nt]
+            HIP_OK(hipMalloc(&iovf, nt + 1));
+            HIP_OK(hipMemset(big, 0, nb + 1));
+            HIP_OK(hipMemset(iovf, 0, nt + 1));
             const unsigned sg = (unsigned)((nt + SP_WAVES - 1) / SP_WAVES);
-#define SEAMS(V) k_seams<V><<<sg, SP_WAVES * 64, 0, s>>>(g, FACES, COUNT, pairs, pc, big, ipairs, ipc, iovf, 0, nt, nullptr)
-            r.push_back({"k_seams_stage", time_ms(s, iters, [&] { SEAMS(1); })});
-            r.push_back({"k_seams_z", time_ms(s, iters, [&] { SEAMS(2); })});
-            r.push_back({"k_seams_zy", time_ms(s, iters, [&] { SEAMS(3); })});
-            r.push_back({"k_seams_zyx", time_ms(s, iters, [&] { SEAMS(4); })});
-            r.push_back({"k_seams_full", time_ms(s, iters, [&] { SEAMS(0); })});
+            r.push_back({"k_seams", time_ms(s, iters, [&] {
+                k_seams<<<sg, SP_WAVES * 64, 0, s>>>(g, FACES, COUNT, pairs, pc, big, ipairs, ipc, iovf, 0, nt, nullptr);
+            })});
         }
         r.push_back({"k_pass2", time_ms(s, iters, [&] { k_pass2<false><<<(unsigned)nt, NTHREADS, 0, s>>>(g, BITS, COUNT, FIN, nullptr, nullptr, 0, 0, out, 0, nullptr, nullptr); })});
         std::printf("{\"shape\": [%lld, %lld, %lld], \"block\": [%lld, %lld, %lld], \"mode\": %d, \"tiles\": %lld",

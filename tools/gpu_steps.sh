@@ -20,12 +20,12 @@
 #   evidence       rocprof summaries of the secondary kernels (threshold, stage path, 8-slab seams of
 #                  both schedules, Gaussian prefilter, resized mask + 4-D normalize, watershed);  prof_c4  C3 + mask with the --narrow correction
 #   clock          effective GPU clock per kernel of the C3 step (tools/pmc_clock.sh)
-#   roof / ablate  the box's streaming ceilings (tools/roof) and the k_spec ablation (tools/ablate)
+#   roof / ablate  the box's streaming ceilings (tools/roof) and the whole-kernel timings (tools/ablate)
 #   ab_fast        same-box round-robin A/B: one-read-back vs host-synchronised schedule (C3)
 #   boxinfo        the lease's static / current SMI info (product, VBIOS, power cap, clocks, memory)
 #   clockprobe     core clock per kernel from in-kernel clock stamps (tools/clock_probe)
 #   slowdiag       a short bench first; only when k_spec runs slow (> 3.3 ms, the driver's slow box
-#                  kind) the box's roof, the k_spec ablation, the clock probe and the PMC passes
+#                  kind) the box's roof, the kernel timings, the clock probe and the PMC passes
 #                  (TCP latency / UTCL1, SQ instruction + wait counters) -> *_slow_TAG
 set -e -o pipefail
 TAG=$1; shift

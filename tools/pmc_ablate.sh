@@ -1,5 +1,5 @@
 #!/bin/bash
-# SQ instruction / wait counters per kernel variant of tools/ablate (one PMC pass).
+# SQ instruction / wait counters per kernel of tools/ablate (one PMC pass).
 # Usage: tools/pmc_ablate.sh OUTDIR Z Y X bz by bx mode
 set -e
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}

@@ -1,5 +1,5 @@
 #!/bin/bash
-# L2 -> memory (TCC_EA) request / stall counters per kernel variant of tools/ablate, two passes of
+# L2 -> memory (TCC_EA) request / stall counters per kernel of tools/ablate, two passes of
 # at most 4 TCC counters each (MI355X_MICROARCH.md: no counter splitting across passes).
 # Usage: tools/pmc_tcc.sh OUTDIR   -> gpurun_out/OUTDIR/{p1,p2}
 set -e
