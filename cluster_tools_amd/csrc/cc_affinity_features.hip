@@ -111,131 +111,113 @@ __global__ __launch_bounds__(GR_WG) void k_aff_feat(const u64* __restrict__ lab,
 
 }  // namespace cc
 
-static int affinity_features_impl(cc_ctx* c, const uint64_t* labels, const void* affinities, int value_type,
-                                  const int64_t shape[3], int n_offsets, const int64_t* offsets, int ignore_label,
-                                  uint64_t* n_edges, uint64_t* edges_host, uint64_t* counts_host, double* sums_host,
-                                  double* sumsq_host, float* mins_host, float* maxs_host, double* quant_host,
-                                  uint32_t* hist_host, int64_t edge_cap) {
-    CC_REQUIRE(c && shape && n_edges && edge_cap >= 0, "bad arguments");
-    CC_REQUIRE(value_type == CC_RF_FLOAT32 || value_type == CC_RF_UINT8, "value_type must be CC_RF_FLOAT32 or CC_RF_UINT8");
-    CC_REQUIRE(edges_host && counts_host && sums_host && sumsq_host && mins_host && maxs_host && quant_host,
-               "affinity features: only hist_host may be null");
-    CC_REQUIRE(n_offsets >= 1 && n_offsets <= AF_MAX, "affinity features: the number of offsets must be in [1, 64]");
-    CC_REQUIRE(offsets, "affinity features: offsets must be a host array of 3 n int64");
-    for (int t = 0; t < n_offsets; ++t)
-        CC_REQUIRE(offsets[3 * t] != 0 || offsets[3 * t + 1] != 0 || offsets[3 * t + 2] != 0,
-                   "affinity features: an offset (0, 0, 0) pairs every voxel with itself");
-    HIP_OK(hipSetDevice(c->device));
-    hipStream_t s = cstream(c);
-    *n_edges = 0;
-    const bool f32 = value_type == CC_RF_FLOAT32;
-    GrPass p;
-    if (!gr_pass(c, labels, shape, shape, ignore_label, edge_cap, p)) return 0;
-    CC_REQUIRE(affinities && (!f32 || ((uintptr_t)affinities & 3) == 0),
-               "affinities must be a device pointer (float32: 4-byte aligned)");
-    const int64_t cap = p.cap, ne = p.ne;
-    *n_edges = (uint64_t)ne;
-    if (ne == 0 || edge_cap < ne) return 0;
-    // an offset as long as an extent gives no sample
-    AfOffs offs;
-    offs.n = 0;
-    for (int t = 0; t < n_offsets; ++t) {
-        const int64_t* d = offsets + 3 * t;
-        bool in = true;
-        for (int a = 0; a < 3; ++a) in = in && d[a] > -shape[a] && d[a] < shape[a];
-        if (!in) continue;
-        offs.c[offs.n] = t; offs.dz[offs.n] = (int)d[0]; offs.dy[offs.n] = (int)d[1]; offs.dx[offs.n] = (int)d[2];
-        ++offs.n;
-    }
-    // pass 1's edges: sorted keys | sizes | rows (u, v); each edge's rank into the key table
-    u64* keys = c->gr_tab.as<u64>();
-    u64* rank = keys + cap;
-    u64* comp = c->gr_comp.as<u64>();
-    c->gr_sorted.ensure((size_t)(4 * ne + 4) * sizeof(u64));
-    u64* ekey = c->gr_sorted.as<u64>();
-    u64* ecnt = ekey + ne + 1;
-    u64* uv = ecnt + ne + 1;
-    launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp + cap, ekey, comp + 2 * cap, ecnt, ne, 0, 64, c->cub_tmp, s); });
-    launch(c, "k_gr_unpack", [&] { k_gr_unpack<<<grid1d(ne), 256, 0, s>>>(ekey, ne, uv); });
-    launch(c, "k_ef_rank", [&] { k_ef_rank<<<grid1d(ne), 256, 0, s>>>(ekey, ne, keys, rank, (u64)cap - 1); });
-    HIP_OK(hipMemcpyAsync(edges_host, uv, 2 * ne * sizeof(u64), hipMemcpyDeviceToHost, s));
-    // per edge: hist (1 KiB) | sum | sumsq | quantiles (f64) | counts (u64) | kmn | kmx (u32) | minima | maxima (f32)
-    const size_t per_edge = EF_BINS * sizeof(u32) + (2 + EF_NQ) * sizeof(double) + sizeof(u64) + 2 * sizeof(u32) + 2 * sizeof(float);
-    const size_t need = (size_t)ne * per_edge;
-    if (c->ef_tab.bytes < need) {                     // a new piece (DevBuf::ensure asks for need + need / 8)
-        size_t free_b = 0, total_b = 0;
-        HIP_OK(hipMemGetInfo(&free_b, &total_b));
-        CC_REQUIRE(need + need / 8 + (size_t(4) << 20) <= free_b,
-                   "affinity features: the per-edge histograms (1 KiB per edge) do not fit the free device memory");
-    }
-    c->ef_tab.ensure(need);
-    EfAcc o;
-    o.hist = c->ef_tab.as<u32>();
-    o.sum = reinterpret_cast<double*>(o.hist + (size_t)ne * EF_BINS);
-    o.sumsq = o.sum + ne;
-    double* quant = o.sumsq + ne;
-    u64* cnt = reinterpret_cast<u64*>(quant + (size_t)ne * EF_NQ);
-    o.kmn = reinterpret_cast<u32*>(cnt + ne);
-    o.kmx = o.kmn + ne;
-    float* mins = reinterpret_cast<float*>(o.kmx + ne);
-    float* maxs = mins + ne;
-    // hist, sum, sumsq, quantiles, counts: zero; the keys: the identities of min and max
-    HIP_OK(hipMemsetAsync(o.hist, 0, (size_t)ne * (EF_BINS * sizeof(u32) + (2 + EF_NQ) * sizeof(double) + sizeof(u64)), s));
-    launch(c, "k_aff_init", [&] { k_aff_init<<<grid1d(ne), 256, 0, s>>>(o.kmn, o.kmx, ne); });
-    if (offs.n) {
-        const int64_t Z = shape[0], Y = shape[1], X = shape[2];
-        const int64_t ntx = (X + 63) / 64, ntiles = ntx * ((Z * Y + AF_R - 1) / AF_R);
-        const int64_t grid = (ntiles + GR_WAVES - 1) / GR_WAVES;
-        CC_REQUIRE(grid < (1LL << 31), "affinity features: too many tiles");
-        launch(c, "k_aff_feat", [&] {
-            if (f32)
-                k_aff_feat<float><<<(unsigned)grid, GR_WG, 0, s>>>(labels, static_cast<const float*>(affinities), Z, Y, X, ntx,
-                                                                  ntiles, offs, ignore_label ? 1 : 0, keys, rank,
-                                                                  (u64)cap - 1, (u32)ne, o, cnt);
-            else
-                k_aff_feat<unsigned char><<<(unsigned)grid, GR_WG, 0, s>>>(labels, static_cast<const unsigned char*>(affinities),
-                                                                          Z, Y, X, ntx, ntiles, offs, ignore_label ? 1 : 0,
-                                                                          keys, rank, (u64)cap - 1, (u32)ne, o, cnt);
-        });
-    }
-    launch(c, "k_ef_quant", [&] {
-        const unsigned qgrid = grid1d(ne * 64);
-        if (f32) k_ef_quant<false><<<qgrid, 256, 0, s>>>(o, cnt, ne, quant, mins, maxs);
-        else k_ef_quant<true><<<qgrid, 256, 0, s>>>(o, cnt, ne, quant, mins, maxs);
-    });
-    HIP_OK(hipMemcpyAsync(counts_host, cnt, (size_t)ne * sizeof(u64), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(sums_host, o.sum, (size_t)ne * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(sumsq_host, o.sumsq, (size_t)ne * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(quant_host, quant, (size_t)ne * EF_NQ * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(mins_host, mins, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(maxs_host, maxs, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (hist_host) HIP_OK(hipMemcpyAsync(hist_host, o.hist, (size_t)ne * EF_BINS * sizeof(u32), hipMemcpyDeviceToHost, s));
-    sync(c);
-    for (int64_t i = 0; i < ne; ++i)
-        CC_REQUIRE(counts_host[i] < (1ull << 32), "affinity features: an edge with 2^32 or more samples (the device bins are 32-bit)");
-    return 0;
-}
 
 extern "C" {
 
-int cc_affinity_features(cc_ctx* c, const uint64_t* labels, const void* affinities, int value_type, const int64_t shape[3],
-                         int n_offsets, const int64_t* offsets, int ignore_label, uint64_t* n_edges, uint64_t* edges_host,
-                         uint64_t* counts_host, double* sums_host, double* sumsq_host, float* mins_host, float* maxs_host,
-                         double* quant_host, uint32_t* hist_host, int64_t edge_cap) {
-    try {
-        return affinity_features_impl(c, labels, affinities, value_type, shape, n_offsets, offsets, ignore_label, n_edges,
-                                      edges_host, counts_host, sums_host, sumsq_host, mins_host, maxs_host, quant_host,
-                                      hist_host, edge_cap);
-    } catch (const CCIdRangeError& e) {
-        g_err = e.msg;
-        return CC_ERR_ID_RANGE;
-    } catch (const CCError& e) {
-        g_err = e.msg;
-        return -1;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return -2;
-    }
+int cc_affinity_features(cc_ctx* c, const uint64_t* labels, const void* affinities, int value_type,
+                         const int64_t shape[3], int n_offsets, const int64_t* offsets, int ignore_label,
+                         uint64_t* n_edges, uint64_t* edges_host, uint64_t* counts_host, double* sums_host,
+                         double* sumsq_host, float* mins_host, float* maxs_host, double* quant_host,
+                         uint32_t* hist_host, int64_t edge_cap) {
+    CC_TRY({
+        CC_REQUIRE(c && shape && n_edges && edge_cap >= 0, "bad arguments");
+        CC_REQUIRE(value_type == CC_RF_FLOAT32 || value_type == CC_RF_UINT8, "value_type must be CC_RF_FLOAT32 or CC_RF_UINT8");
+        CC_REQUIRE(edges_host && counts_host && sums_host && sumsq_host && mins_host && maxs_host && quant_host,
+                   "affinity features: only hist_host may be null");
+        CC_REQUIRE(n_offsets >= 1 && n_offsets <= AF_MAX, "affinity features: the number of offsets must be in [1, 64]");
+        CC_REQUIRE(offsets, "affinity features: offsets must be a host array of 3 n int64");
+        for (int t = 0; t < n_offsets; ++t)
+            CC_REQUIRE(offsets[3 * t] != 0 || offsets[3 * t + 1] != 0 || offsets[3 * t + 2] != 0,
+                       "affinity features: an offset (0, 0, 0) pairs every voxel with itself");
+        HIP_OK(hipSetDevice(c->device));
+        hipStream_t s = cstream(c);
+        *n_edges = 0;
+        const bool f32 = value_type == CC_RF_FLOAT32;
+        GrPass p;
+        if (!gr_pass(c, labels, shape, shape, ignore_label, edge_cap, p)) return 0;
+        CC_REQUIRE(affinities && (!f32 || ((uintptr_t)affinities & 3) == 0),
+                   "affinities must be a device pointer (float32: 4-byte aligned)");
+        const int64_t cap = p.cap, ne = p.ne;
+        *n_edges = (uint64_t)ne;
+        if (ne == 0 || edge_cap < ne) return 0;
+        // an offset as long as an extent gives no sample
+        AfOffs offs;
+        offs.n = 0;
+        for (int t = 0; t < n_offsets; ++t) {
+            const int64_t* d = offsets + 3 * t;
+            bool in = true;
+            for (int a = 0; a < 3; ++a) in = in && d[a] > -shape[a] && d[a] < shape[a];
+            if (!in) continue;
+            offs.c[offs.n] = t; offs.dz[offs.n] = (int)d[0]; offs.dy[offs.n] = (int)d[1]; offs.dx[offs.n] = (int)d[2];
+            ++offs.n;
+        }
+        // pass 1's edges: sorted keys | sizes | rows (u, v); each edge's rank into the key table
+        u64* keys = c->gr_tab.as<u64>();
+        u64* rank = keys + cap;
+        u64* comp = c->gr_comp.as<u64>();
+        c->gr_sorted.ensure((size_t)(4 * ne + 4) * sizeof(u64));
+        u64* ekey = c->gr_sorted.as<u64>();
+        u64* ecnt = ekey + ne + 1;
+        u64* uv = ecnt + ne + 1;
+        launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp + cap, ekey, comp + 2 * cap, ecnt, ne, 0, 64, c->cub_tmp, s); });
+        launch(c, "k_gr_unpack", [&] { k_gr_unpack<<<grid1d(ne), 256, 0, s>>>(ekey, ne, uv); });
+        launch(c, "k_ef_rank", [&] { k_ef_rank<<<grid1d(ne), 256, 0, s>>>(ekey, ne, keys, rank, (u64)cap - 1); });
+        HIP_OK(hipMemcpyAsync(edges_host, uv, 2 * ne * sizeof(u64), hipMemcpyDeviceToHost, s));
+        // per edge: hist (1 KiB) | sum | sumsq | quantiles (f64) | counts (u64) | kmn | kmx (u32) | minima | maxima (f32)
+        const size_t per_edge = EF_BINS * sizeof(u32) + (2 + EF_NQ) * sizeof(double) + sizeof(u64) + 2 * sizeof(u32) + 2 * sizeof(float);
+        const size_t need = (size_t)ne * per_edge;
+        if (c->ef_tab.bytes < need) {                     // a new piece (DevBuf::ensure asks for need + need / 8)
+            size_t free_b = 0, total_b = 0;
+            HIP_OK(hipMemGetInfo(&free_b, &total_b));
+            CC_REQUIRE(need + need / 8 + (size_t(4) << 20) <= free_b,
+                       "affinity features: the per-edge histograms (1 KiB per edge) do not fit the free device memory");
+        }
+        c->ef_tab.ensure(need);
+        EfAcc o;
+        o.hist = c->ef_tab.as<u32>();
+        o.sum = reinterpret_cast<double*>(o.hist + (size_t)ne * EF_BINS);
+        o.sumsq = o.sum + ne;
+        double* quant = o.sumsq + ne;
+        u64* cnt = reinterpret_cast<u64*>(quant + (size_t)ne * EF_NQ);
+        o.kmn = reinterpret_cast<u32*>(cnt + ne);
+        o.kmx = o.kmn + ne;
+        float* mins = reinterpret_cast<float*>(o.kmx + ne);
+        float* maxs = mins + ne;
+        // hist, sum, sumsq, quantiles, counts: zero; the keys: the identities of min and max
+        HIP_OK(hipMemsetAsync(o.hist, 0, (size_t)ne * (EF_BINS * sizeof(u32) + (2 + EF_NQ) * sizeof(double) + sizeof(u64)), s));
+        launch(c, "k_aff_init", [&] { k_aff_init<<<grid1d(ne), 256, 0, s>>>(o.kmn, o.kmx, ne); });
+        if (offs.n) {
+            const int64_t Z = shape[0], Y = shape[1], X = shape[2];
+            const int64_t ntx = (X + 63) / 64, ntiles = ntx * ((Z * Y + AF_R - 1) / AF_R);
+            const int64_t grid = (ntiles + GR_WAVES - 1) / GR_WAVES;
+            CC_REQUIRE(grid < (1LL << 31), "affinity features: too many tiles");
+            launch(c, "k_aff_feat", [&] {
+                if (f32)
+                    k_aff_feat<float><<<(unsigned)grid, GR_WG, 0, s>>>(labels, static_cast<const float*>(affinities), Z, Y, X, ntx,
+                                                                      ntiles, offs, ignore_label ? 1 : 0, keys, rank,
+                                                                      (u64)cap - 1, (u32)ne, o, cnt);
+                else
+                    k_aff_feat<unsigned char><<<(unsigned)grid, GR_WG, 0, s>>>(labels, static_cast<const unsigned char*>(affinities),
+                                                                              Z, Y, X, ntx, ntiles, offs, ignore_label ? 1 : 0,
+                                                                              keys, rank, (u64)cap - 1, (u32)ne, o, cnt);
+            });
+        }
+        launch(c, "k_ef_quant", [&] {
+            const unsigned qgrid = grid1d(ne * 64);
+            if (f32) k_ef_quant<false><<<qgrid, 256, 0, s>>>(o, cnt, ne, quant, mins, maxs);
+            else k_ef_quant<true><<<qgrid, 256, 0, s>>>(o, cnt, ne, quant, mins, maxs);
+        });
+        HIP_OK(hipMemcpyAsync(counts_host, cnt, (size_t)ne * sizeof(u64), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(sums_host, o.sum, (size_t)ne * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(sumsq_host, o.sumsq, (size_t)ne * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(quant_host, quant, (size_t)ne * EF_NQ * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(mins_host, mins, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(maxs_host, maxs, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (hist_host) HIP_OK(hipMemcpyAsync(hist_host, o.hist, (size_t)ne * EF_BINS * sizeof(u32), hipMemcpyDeviceToHost, s));
+        sync(c);
+        for (int64_t i = 0; i < ne; ++i)
+            CC_REQUIRE(counts_host[i] < (1ull << 32), "affinity features: an edge with 2^32 or more samples (the device bins are 32-bit)");
+    })
 }
 
 }  // extern "C"

@@ -489,12 +489,16 @@ static RunState& state(cc_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------
-// C ABI error convention: 0 ok, -1 CCError (message in cc_last_error), -2 other exceptions
+// C ABI error convention: 0 ok, -1 CCError (message in cc_last_error), -2 other exceptions,
+// CC_ERR_ID_RANGE CCIdRangeError (thrown by the entries whose keys pack ids)
 // ------------------------------------------------------------------------------------------
 #define CC_TRY(...)                                                                            \
     try {                                                                                      \
         __VA_ARGS__;                                                                           \
         return 0;                                                                              \
+    } catch (const CCIdRangeError& e) {                                                        \
+        g_err = e.msg;                                                                         \
+        return CC_ERR_ID_RANGE;                                                                \
     } catch (const CCError& e) {                                                               \
         g_err = e.msg;                                                                         \
         return -1;                                                                             \

@@ -45,6 +45,7 @@ __device__ __forceinline__ u32 ef_bin(float s) {
 }
 
 // rank of an edge key in the table of pass 1 (read only); EF_NONE when it is not there
+// (not tab_find, which hands back the free slot that ends a miss: the key would be loaded twice)
 __device__ __noinline__ u32 ef_lookup(const u64* __restrict__ keys, const u64* __restrict__ rank, u64 mask, u64 key) {
     u64 h = ev_hash(key) & mask;
 #pragma unroll 1
@@ -226,113 +227,95 @@ __global__ __launch_bounds__(256) void k_ef_quant(EfAcc o, const u64* __restrict
 
 }  // namespace cc
 
-static int edge_features_impl(cc_ctx* c, const uint64_t* labels, const void* values, int value_type,
-                              const int64_t shape[3], const int64_t owned[3], int ignore_label, uint64_t* n_edges,
-                              uint64_t* edges_host, uint64_t* counts_host, double* sums_host, double* sumsq_host,
-                              float* mins_host, float* maxs_host, double* quant_host, uint32_t* hist_host,
-                              int64_t edge_cap) {
-    CC_REQUIRE(c && shape && owned && n_edges && edge_cap >= 0, "bad arguments");
-    CC_REQUIRE(value_type == CC_RF_FLOAT32 || value_type == CC_RF_UINT8, "value_type must be CC_RF_FLOAT32 or CC_RF_UINT8");
-    CC_REQUIRE(edges_host && counts_host && sums_host && sumsq_host && mins_host && maxs_host && quant_host,
-               "edge features: only hist_host may be null");
-    HIP_OK(hipSetDevice(c->device));
-    hipStream_t s = cstream(c);
-    *n_edges = 0;
-    const bool f32 = value_type == CC_RF_FLOAT32;
-    GrPass p;
-    if (!gr_pass(c, labels, shape, owned, ignore_label, edge_cap, p)) return 0;
-    CC_REQUIRE(values && (!f32 || ((uintptr_t)values & 3) == 0), "values must be a device pointer (float32: 4-byte aligned)");
-    const int64_t cap = p.cap, ne = p.ne;
-    *n_edges = (uint64_t)ne;
-    if (ne == 0 || edge_cap < ne) return 0;
-    // pass 1's edges: sorted keys | sizes | rows (u, v); each edge's rank into the key table
-    u64* keys = c->gr_tab.as<u64>();
-    u64* rank = keys + cap;
-    u64* comp = c->gr_comp.as<u64>();
-    c->gr_sorted.ensure((size_t)(4 * ne + 4) * sizeof(u64));
-    u64* ekey = c->gr_sorted.as<u64>();
-    u64* ecnt = ekey + ne + 1;
-    u64* uv = ecnt + ne + 1;
-    launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp + cap, ekey, comp + 2 * cap, ecnt, ne, 0, 64, c->cub_tmp, s); });
-    launch(c, "k_gr_unpack", [&] { k_gr_unpack<<<grid1d(ne), 256, 0, s>>>(ekey, ne, uv); });
-    launch(c, "k_ef_rank", [&] { k_ef_rank<<<grid1d(ne), 256, 0, s>>>(ekey, ne, keys, rank, (u64)cap - 1); });
-    HIP_OK(hipMemcpyAsync(edges_host, uv, 2 * ne * sizeof(u64), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(counts_host, ecnt, ne * sizeof(u64), hipMemcpyDeviceToHost, s));
-    sync(c);
-    for (int64_t i = 0; i < ne; ++i)
-        CC_REQUIRE(counts_host[i] < (1ull << 32), "edge features: an edge with 2^32 or more faces (the device bins are 32-bit)");
-    // per edge: hist (1 KiB) | sum | sumsq | quantiles (f64) | kmn | kmx (u32) | minima | maxima (f32)
-    const size_t per_edge = EF_BINS * sizeof(u32) + (2 + EF_NQ) * sizeof(double) + 2 * sizeof(u32) + 2 * sizeof(float);
-    const size_t need = (size_t)ne * per_edge;
-    if (c->ef_tab.bytes < need) {                     // a new piece (DevBuf::ensure asks for need + need / 8)
-        size_t free_b = 0, total_b = 0;
-        HIP_OK(hipMemGetInfo(&free_b, &total_b));
-        CC_REQUIRE(need + need / 8 + (size_t(4) << 20) <= free_b,
-                   "edge features: the per-edge histograms (1 KiB per edge) do not fit the free device memory");
-    }
-    c->ef_tab.ensure(need);
-    EfAcc o;
-    o.hist = c->ef_tab.as<u32>();
-    o.sum = reinterpret_cast<double*>(o.hist + (size_t)ne * EF_BINS);
-    o.sumsq = o.sum + ne;
-    double* quant = o.sumsq + ne;
-    o.kmn = reinterpret_cast<u32*>(quant + (size_t)ne * EF_NQ);
-    o.kmx = o.kmn + ne;
-    float* mins = reinterpret_cast<float*>(o.kmx + ne);
-    float* maxs = mins + ne;
-    // hist, sum, sumsq, quantiles: zero; minimum keys: all ones; maximum keys: zero
-    HIP_OK(hipMemsetAsync(o.hist, 0, (size_t)ne * (EF_BINS * sizeof(u32) + (2 + EF_NQ) * sizeof(double)), s));
-    HIP_OK(hipMemsetAsync(o.kmn, 0xFF, (size_t)ne * sizeof(u32), s));
-    HIP_OK(hipMemsetAsync(o.kmx, 0, (size_t)ne * sizeof(u32), s));
-    HIP_OK(hipMemsetAsync(c->counter.p, 0, sizeof(u32), s));
-    u32* err = c->counter.as<u32>();
-    const GrGeom g = gr_geom(shape, owned, EF_R);
-    const unsigned grid = gr_grid(g);
-    launch(c, "k_edge_feat", [&] {
-        if (f32)
-            k_edge_feat<float><<<grid, GR_WG, 0, s>>>(labels, static_cast<const float*>(values), g, ignore_label ? 1 : 0, keys,
-                                                     rank, (u64)cap - 1, (u32)ne, o, err);
-        else
-            k_edge_feat<unsigned char><<<grid, GR_WG, 0, s>>>(labels, static_cast<const unsigned char*>(values), g,
-                                                             ignore_label ? 1 : 0, keys, rank, (u64)cap - 1, (u32)ne, o, err);
-    });
-    launch(c, "k_ef_quant", [&] {
-        const unsigned qgrid = grid1d(ne * 64);
-        if (f32) k_ef_quant<false><<<qgrid, 256, 0, s>>>(o, ecnt, ne, quant, mins, maxs);
-        else k_ef_quant<true><<<qgrid, 256, 0, s>>>(o, ecnt, ne, quant, mins, maxs);
-    });
-    u32 h = 0;
-    HIP_OK(hipMemcpyAsync(&h, err, sizeof(u32), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(sums_host, o.sum, (size_t)ne * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(sumsq_host, o.sumsq, (size_t)ne * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(quant_host, quant, (size_t)ne * EF_NQ * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(mins_host, mins, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(maxs_host, maxs, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (hist_host) HIP_OK(hipMemcpyAsync(hist_host, o.hist, (size_t)ne * EF_BINS * sizeof(u32), hipMemcpyDeviceToHost, s));
-    sync(c);
-    CC_REQUIRE(!(h & EF_ERR_LOOKUP), "edge features: a face's edge is missing from the graph pass (the labels changed between the passes?)");
-    return 0;
-}
 
 extern "C" {
 
 int cc_edge_features(cc_ctx* c, const uint64_t* labels, const void* values, int value_type, const int64_t shape[3],
                      const int64_t owned[3], int ignore_label, uint64_t* n_edges, uint64_t* edges_host,
-                     uint64_t* counts_host, double* sums_host, double* sumsq_host, float* mins_host, float* maxs_host,
-                     double* quant_host, uint32_t* hist_host, int64_t edge_cap) {
-    try {
-        return edge_features_impl(c, labels, values, value_type, shape, owned, ignore_label, n_edges, edges_host,
-                                  counts_host, sums_host, sumsq_host, mins_host, maxs_host, quant_host, hist_host, edge_cap);
-    } catch (const CCIdRangeError& e) {
-        g_err = e.msg;
-        return CC_ERR_ID_RANGE;
-    } catch (const CCError& e) {
-        g_err = e.msg;
-        return -1;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return -2;
-    }
+                     uint64_t* counts_host, double* sums_host, double* sumsq_host, float* mins_host,
+                     float* maxs_host, double* quant_host, uint32_t* hist_host, int64_t edge_cap) {
+    CC_TRY({
+        CC_REQUIRE(c && shape && owned && n_edges && edge_cap >= 0, "bad arguments");
+        CC_REQUIRE(value_type == CC_RF_FLOAT32 || value_type == CC_RF_UINT8, "value_type must be CC_RF_FLOAT32 or CC_RF_UINT8");
+        CC_REQUIRE(edges_host && counts_host && sums_host && sumsq_host && mins_host && maxs_host && quant_host,
+                   "edge features: only hist_host may be null");
+        HIP_OK(hipSetDevice(c->device));
+        hipStream_t s = cstream(c);
+        *n_edges = 0;
+        const bool f32 = value_type == CC_RF_FLOAT32;
+        GrPass p;
+        if (!gr_pass(c, labels, shape, owned, ignore_label, edge_cap, p)) return 0;
+        CC_REQUIRE(values && (!f32 || ((uintptr_t)values & 3) == 0), "values must be a device pointer (float32: 4-byte aligned)");
+        const int64_t cap = p.cap, ne = p.ne;
+        *n_edges = (uint64_t)ne;
+        if (ne == 0 || edge_cap < ne) return 0;
+        // pass 1's edges: sorted keys | sizes | rows (u, v); each edge's rank into the key table
+        u64* keys = c->gr_tab.as<u64>();
+        u64* rank = keys + cap;
+        u64* comp = c->gr_comp.as<u64>();
+        c->gr_sorted.ensure((size_t)(4 * ne + 4) * sizeof(u64));
+        u64* ekey = c->gr_sorted.as<u64>();
+        u64* ecnt = ekey + ne + 1;
+        u64* uv = ecnt + ne + 1;
+        launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp + cap, ekey, comp + 2 * cap, ecnt, ne, 0, 64, c->cub_tmp, s); });
+        launch(c, "k_gr_unpack", [&] { k_gr_unpack<<<grid1d(ne), 256, 0, s>>>(ekey, ne, uv); });
+        launch(c, "k_ef_rank", [&] { k_ef_rank<<<grid1d(ne), 256, 0, s>>>(ekey, ne, keys, rank, (u64)cap - 1); });
+        HIP_OK(hipMemcpyAsync(edges_host, uv, 2 * ne * sizeof(u64), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(counts_host, ecnt, ne * sizeof(u64), hipMemcpyDeviceToHost, s));
+        sync(c);
+        for (int64_t i = 0; i < ne; ++i)
+            CC_REQUIRE(counts_host[i] < (1ull << 32), "edge features: an edge with 2^32 or more faces (the device bins are 32-bit)");
+        // per edge: hist (1 KiB) | sum | sumsq | quantiles (f64) | kmn | kmx (u32) | minima | maxima (f32)
+        const size_t per_edge = EF_BINS * sizeof(u32) + (2 + EF_NQ) * sizeof(double) + 2 * sizeof(u32) + 2 * sizeof(float);
+        const size_t need = (size_t)ne * per_edge;
+        if (c->ef_tab.bytes < need) {                     // a new piece (DevBuf::ensure asks for need + need / 8)
+            size_t free_b = 0, total_b = 0;
+            HIP_OK(hipMemGetInfo(&free_b, &total_b));
+            CC_REQUIRE(need + need / 8 + (size_t(4) << 20) <= free_b,
+                       "edge features: the per-edge histograms (1 KiB per edge) do not fit the free device memory");
+        }
+        c->ef_tab.ensure(need);
+        EfAcc o;
+        o.hist = c->ef_tab.as<u32>();
+        o.sum = reinterpret_cast<double*>(o.hist + (size_t)ne * EF_BINS);
+        o.sumsq = o.sum + ne;
+        double* quant = o.sumsq + ne;
+        o.kmn = reinterpret_cast<u32*>(quant + (size_t)ne * EF_NQ);
+        o.kmx = o.kmn + ne;
+        float* mins = reinterpret_cast<float*>(o.kmx + ne);
+        float* maxs = mins + ne;
+        // hist, sum, sumsq, quantiles: zero; minimum keys: all ones; maximum keys: zero
+        HIP_OK(hipMemsetAsync(o.hist, 0, (size_t)ne * (EF_BINS * sizeof(u32) + (2 + EF_NQ) * sizeof(double)), s));
+        HIP_OK(hipMemsetAsync(o.kmn, 0xFF, (size_t)ne * sizeof(u32), s));
+        HIP_OK(hipMemsetAsync(o.kmx, 0, (size_t)ne * sizeof(u32), s));
+        HIP_OK(hipMemsetAsync(c->counter.p, 0, sizeof(u32), s));
+        u32* err = c->counter.as<u32>();
+        const GrGeom g = gr_geom(shape, owned, EF_R);
+        const unsigned grid = gr_grid(g);
+        launch(c, "k_edge_feat", [&] {
+            if (f32)
+                k_edge_feat<float><<<grid, GR_WG, 0, s>>>(labels, static_cast<const float*>(values), g, ignore_label ? 1 : 0, keys,
+                                                         rank, (u64)cap - 1, (u32)ne, o, err);
+            else
+                k_edge_feat<unsigned char><<<grid, GR_WG, 0, s>>>(labels, static_cast<const unsigned char*>(values), g,
+                                                                 ignore_label ? 1 : 0, keys, rank, (u64)cap - 1, (u32)ne, o, err);
+        });
+        launch(c, "k_ef_quant", [&] {
+            const unsigned qgrid = grid1d(ne * 64);
+            if (f32) k_ef_quant<false><<<qgrid, 256, 0, s>>>(o, ecnt, ne, quant, mins, maxs);
+            else k_ef_quant<true><<<qgrid, 256, 0, s>>>(o, ecnt, ne, quant, mins, maxs);
+        });
+        u32 h = 0;
+        HIP_OK(hipMemcpyAsync(&h, err, sizeof(u32), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(sums_host, o.sum, (size_t)ne * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(sumsq_host, o.sumsq, (size_t)ne * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(quant_host, quant, (size_t)ne * EF_NQ * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(mins_host, mins, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(maxs_host, maxs, (size_t)ne * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (hist_host) HIP_OK(hipMemcpyAsync(hist_host, o.hist, (size_t)ne * EF_BINS * sizeof(u32), hipMemcpyDeviceToHost, s));
+        sync(c);
+        CC_REQUIRE(!(h & EF_ERR_LOOKUP), "edge features: a face's edge is missing from the graph pass (the labels changed between the passes?)");
+    })
 }
 
 }  // extern "C"

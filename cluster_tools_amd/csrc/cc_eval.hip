@@ -25,41 +25,14 @@
 
 namespace cc {
 
-constexpr u64 EV_EMPTY = ~0ull;
 constexpr u64 EV_ZTAG = 1ull << 63;
-constexpr int EV_LDS = 2048;       // LDS hash entries per workgroup
-constexpr int EV_LDS_PROBES = 32;
-constexpr int EV_PROBES = 1024;    // global probe limit before reporting the table as full (a full
-                                   // table costs every further insert this many probes before the rerun)
 constexpr int EV_Q = 8;            // loads of 64 voxels per wave item
 constexpr int EV_ROW = 64 * EV_Q;  // voxels of one row per wave item
-constexpr u32 EV_ERR_SEG = 1, EV_ERR_GT = 2, EV_ERR_FULL = 4;
+constexpr u32 EV_ERR_SEG = 1, EV_ERR_GT = 2;   // beside EV_ERR_FULL
 
-__device__ __forceinline__ u64 ev_hash(u64 k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
-
-// global open-addressing insert (linear probing); false when EV_PROBES slots were taken
+// add c to the count of `key` in an HBM table (tab_upsert); false when the table is full
 __device__ bool ev_insert(u64* keys, u64* cnts, u64 mask, u64 key, u64 c) {
-    u64 h = ev_hash(key) & mask;
-    for (int probe = 0; probe < EV_PROBES; ++probe) {
-        u64 k = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == EV_EMPTY) {
-            k = atomicCAS((unsigned long long*)&keys[h], (unsigned long long)EV_EMPTY, (unsigned long long)key);
-            if (k == EV_EMPTY) k = key;
-        }
-        if (k == key) {
-            atomicAdd((unsigned long long*)&cnts[h], (unsigned long long)c);
-            return true;
-        }
-        h = (h + 1) & mask;
-    }
-    return false;
+    return tab_upsert(keys, mask, key, [&](u64 h) { atomicAdd((unsigned long long*)&cnts[h], (unsigned long long)c); });
 }
 
 // the occupied slots of a (keys, counts) table, in any order (a sort follows); *count = their
@@ -87,6 +60,9 @@ __device__ __forceinline__ void ev_global(const EvTabs& t, u64 key, u64 c) {
     if (!ok) atomicOr(t.err, EV_ERR_FULL);
 }
 
+// add (key, c) to the workgroup's LDS table.  lds_upsert's loop written out: this one is left to the
+// compiler to unroll, and through the helper its kernels compiled to other code ("The
+// table pass")
 __device__ __forceinline__ void ev_local(u64* lk, u32* lc, const EvTabs& t, u64 key, u32 c) {
     u32 h = (u32)ev_hash(key) & (EV_LDS - 1);
     for (int probe = 0; probe < EV_LDS_PROBES; ++probe) {
@@ -277,36 +253,11 @@ static EvSums ev_table_sums(cc_ctx* c, const u64* keys, const u64* cnts, int64_t
     return r;
 }
 
-// ids beyond the 64-bit key packing: reported with their own status (CC_ERR_ID_RANGE) so a caller
-// can relabel and retry without parsing the message
-struct CCIdRangeError : CCError {};
-
-static int evaluate_impl(cc_ctx* c, const uint64_t* seg, const uint64_t* gt, const int64_t shape[3],
-                         const int64_t block_shape[3], int use_ignore, uint64_t ignore_label, cc_eval_result* out);
-
 extern "C" {
 
 int cc_evaluate(cc_ctx* c, const uint64_t* seg, const uint64_t* gt, const int64_t shape[3],
                 const int64_t block_shape[3], int use_ignore, uint64_t ignore_label, cc_eval_result* out) {
-    try {
-        return evaluate_impl(c, seg, gt, shape, block_shape, use_ignore, ignore_label, out);
-    } catch (const CCIdRangeError& e) {
-        g_err = e.msg;
-        return CC_ERR_ID_RANGE;
-    } catch (const CCError& e) {
-        g_err = e.msg;
-        return -1;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return -2;
-    }
-}
-
-}  // extern "C"
-
-static int evaluate_impl(cc_ctx* c, const uint64_t* seg, const uint64_t* gt, const int64_t shape[3],
-                         const int64_t block_shape[3], int use_ignore, uint64_t ignore_label, cc_eval_result* out) {
-    {
+    CC_TRY({
         CC_REQUIRE(c && seg && gt && shape && block_shape && out, "bad arguments");
         HIP_OK(hipSetDevice(c->device));
         hipStream_t s = cstream(c);
@@ -379,11 +330,8 @@ static int evaluate_impl(cc_ctx* c, const uint64_t* seg, const uint64_t* gt, con
         out->sum_sq_pairs = m.sq;
         out->sum_sq_gt = a.sq;
         out->sum_sq_seg = b.sq;
-        return 0;
-    }
+    })
 }
-
-extern "C" {
 
 int64_t cc_get_overlaps(cc_ctx* c, uint64_t* seg_ids, uint64_t* gt_ids, uint64_t* counts, int64_t cap) {
     try {

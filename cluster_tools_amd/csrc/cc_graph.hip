@@ -55,21 +55,10 @@ __device__ __forceinline__ u64 gr_key(u64 a, u64 b, bool own, bool ignore) {
 // add (key, c) to the workgroup's LDS table; a crowded table sends the add straight to HBM (false
 // when that table is full).  Not inlined: the unrolled row loop of k_graph has four call sites per row
 __device__ __noinline__ bool gr_lds_add(u64* lk, u32* lc, u64* keys, u64* cnts, u64 mask, u64 key, u32 c) {
-    u32 h = rl_lhash(key);
-#pragma unroll 1
-    for (int probe = 0; probe < EV_LDS_PROBES; ++probe) {
-        u64 k = lk[h];
-        if (k == EV_EMPTY) {
-            k = atomicCAS((unsigned long long*)&lk[h], (unsigned long long)EV_EMPTY, (unsigned long long)key);
-            if (k == EV_EMPTY) k = key;
-        }
-        if (k == key) {
-            atomicAdd(&lc[h], c);
-            return true;
-        }
-        h = (h + 1) & (EV_LDS - 1);
-    }
-    return ev_insert(keys, cnts, mask, key, (u64)c);
+    bool ok = true;
+    lds_upsert<EV_LDS>(lk, lds_hash<RL_LDS_BITS>(key), key, [&](u32 h) { atomicAdd(&lc[h], c); },
+                       [&] { ok = ev_insert(keys, cnts, mask, key, (u64)c); });
+    return ok;
 }
 
 __global__ __launch_bounds__(GR_WG) void k_graph(const u64* __restrict__ lab, GrGeom g, int ignore, u64* keys, u64* cnts,
@@ -265,61 +254,45 @@ static bool gr_pass(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], c
     return true;
 }
 
-static int region_graph_impl(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], const int64_t owned[3],
-                             int ignore_label, uint64_t* n_nodes, uint64_t* nodes_host, int64_t node_cap,
-                             uint64_t* n_edges, uint64_t* edges_host, uint64_t* sizes_host, int64_t edge_cap) {
-    CC_REQUIRE(c && shape && owned && n_nodes && n_edges && node_cap >= 0 && edge_cap >= 0, "bad arguments");
-    CC_REQUIRE((edges_host == nullptr) == (sizes_host == nullptr), "edges_host and sizes_host go together");
-    HIP_OK(hipSetDevice(c->device));
-    hipStream_t s = cstream(c);
-    *n_nodes = 0;
-    *n_edges = 0;
-    GrPass p;
-    if (!gr_pass(c, labels, shape, owned, ignore_label, (nodes_host ? node_cap : 0) + (edges_host ? edge_cap : 0), p)) return 0;
-    const int64_t cap = p.cap, nn = p.nn, ne = p.ne;
-    u64* comp = c->gr_comp.as<u64>();
-    *n_nodes = (uint64_t)nn;
-    *n_edges = (uint64_t)ne;
-    if ((nodes_host && node_cap < nn) || (edges_host && edge_cap < ne)) return 0;
-    if (!nodes_host && !edges_host) return 0;
-    // sorted nodes | sorted edge keys | sizes | rows (u, v)
-    c->gr_sorted.ensure((size_t)(nn + 4 * ne + 4) * sizeof(u64));
-    u64* nodes = c->gr_sorted.as<u64>();
-    u64* ekey = nodes + nn + 1;
-    u64* ecnt = ekey + ne + 1;
-    u64* uv = ecnt + ne + 1;
-    if (nodes_host && nn) {
-        launch(c, "radix_sort", [&] { prims::sort_keys<u64>(comp, nodes, nn, 0, 32, c->cub_tmp, s); });
-        HIP_OK(hipMemcpyAsync(nodes_host, nodes, nn * sizeof(u64), hipMemcpyDeviceToHost, s));
-    }
-    if (edges_host && ne) {
-        launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp + cap, ekey, comp + 2 * cap, ecnt, ne, 0, 64, c->cub_tmp, s); });
-        launch(c, "k_gr_unpack", [&] { k_gr_unpack<<<grid1d(ne), 256, 0, s>>>(ekey, ne, uv); });
-        HIP_OK(hipMemcpyAsync(edges_host, uv, 2 * ne * sizeof(u64), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(sizes_host, ecnt, ne * sizeof(u64), hipMemcpyDeviceToHost, s));
-    }
-    sync(c);
-    return 0;
-}
 
 extern "C" {
 
-int cc_region_graph(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], const int64_t owned[3], int ignore_label,
-                    uint64_t* n_nodes, uint64_t* nodes_host, int64_t node_cap, uint64_t* n_edges, uint64_t* edges_host,
-                    uint64_t* sizes_host, int64_t edge_cap) {
-    try {
-        return region_graph_impl(c, labels, shape, owned, ignore_label, n_nodes, nodes_host, node_cap, n_edges, edges_host,
-                                 sizes_host, edge_cap);
-    } catch (const CCIdRangeError& e) {
-        g_err = e.msg;
-        return CC_ERR_ID_RANGE;
-    } catch (const CCError& e) {
-        g_err = e.msg;
-        return -1;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return -2;
-    }
+int cc_region_graph(cc_ctx* c, const uint64_t* labels, const int64_t shape[3], const int64_t owned[3],
+                    int ignore_label, uint64_t* n_nodes, uint64_t* nodes_host, int64_t node_cap, uint64_t* n_edges,
+                    uint64_t* edges_host, uint64_t* sizes_host, int64_t edge_cap) {
+    CC_TRY({
+        CC_REQUIRE(c && shape && owned && n_nodes && n_edges && node_cap >= 0 && edge_cap >= 0, "bad arguments");
+        CC_REQUIRE((edges_host == nullptr) == (sizes_host == nullptr), "edges_host and sizes_host go together");
+        HIP_OK(hipSetDevice(c->device));
+        hipStream_t s = cstream(c);
+        *n_nodes = 0;
+        *n_edges = 0;
+        GrPass p;
+        if (!gr_pass(c, labels, shape, owned, ignore_label, (nodes_host ? node_cap : 0) + (edges_host ? edge_cap : 0), p)) return 0;
+        const int64_t cap = p.cap, nn = p.nn, ne = p.ne;
+        u64* comp = c->gr_comp.as<u64>();
+        *n_nodes = (uint64_t)nn;
+        *n_edges = (uint64_t)ne;
+        if ((nodes_host && node_cap < nn) || (edges_host && edge_cap < ne)) return 0;
+        if (!nodes_host && !edges_host) return 0;
+        // sorted nodes | sorted edge keys | sizes | rows (u, v)
+        c->gr_sorted.ensure((size_t)(nn + 4 * ne + 4) * sizeof(u64));
+        u64* nodes = c->gr_sorted.as<u64>();
+        u64* ekey = nodes + nn + 1;
+        u64* ecnt = ekey + ne + 1;
+        u64* uv = ecnt + ne + 1;
+        if (nodes_host && nn) {
+            launch(c, "radix_sort", [&] { prims::sort_keys<u64>(comp, nodes, nn, 0, 32, c->cub_tmp, s); });
+            HIP_OK(hipMemcpyAsync(nodes_host, nodes, nn * sizeof(u64), hipMemcpyDeviceToHost, s));
+        }
+        if (edges_host && ne) {
+            launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp + cap, ekey, comp + 2 * cap, ecnt, ne, 0, 64, c->cub_tmp, s); });
+            launch(c, "k_gr_unpack", [&] { k_gr_unpack<<<grid1d(ne), 256, 0, s>>>(ekey, ne, uv); });
+            HIP_OK(hipMemcpyAsync(edges_host, uv, 2 * ne * sizeof(u64), hipMemcpyDeviceToHost, s));
+            HIP_OK(hipMemcpyAsync(sizes_host, ecnt, ne * sizeof(u64), hipMemcpyDeviceToHost, s));
+        }
+        sync(c);
+    })
 }
 
 }  // extern "C"

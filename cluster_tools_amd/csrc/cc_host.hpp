@@ -15,6 +15,9 @@ namespace cc {
 struct CCError {
     std::string msg;
 };
+// ids beyond a 64-bit key packing: reported with their own status (CC_ERR_ID_RANGE) so a caller
+// can relabel and retry without parsing the message
+struct CCIdRangeError : CCError {};
 
 #define HIP_OK(expr)                                                                           \
     do {                                                                                       \

@@ -23,10 +23,6 @@ namespace cc {
 constexpr int MO_LDS_BITS = 10;
 constexpr int MO_LDS = 1 << MO_LDS_BITS;
 
-__device__ __forceinline__ u32 mo_lhash(u64 k) {
-    return ((u32)k ^ (u32)(k >> 32) * 0x85EBCA6Bu) * 0x9E3779B1u >> (32 - MO_LDS_BITS);
-}
-
 // t / d, r = t % d for 1 <= d < 2^31 and rcp = floor(2^32 / d) (2^32 - 1 for d = 1): the
 // estimate umulhi(t, rcp) is the quotient or one below it
 __device__ __forceinline__ u32 mo_divmod(u32 t, u32 d, u32 rcp, u32& r) {
@@ -71,30 +67,19 @@ struct MoAcc {
     }
 };
 
-// global open-addressing update (linear probing, as ev_insert); false when EV_PROBES slots were taken
+// update of an id's record in the HBM table (tab_upsert); false when the table is full
 __device__ bool mo_insert(const MoTab& t, u64 key, u64 n, u64 sz, u64 sy, u64 sx, u32 z0, u32 y0, u32 x0, u32 z1,
                           u32 y1, u32 x1) {
-    u64 h = ev_hash(key) & t.mask;
-    for (int probe = 0; probe < EV_PROBES; ++probe) {
-        u64 k = __hip_atomic_load(&t.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == EV_EMPTY) {
-            k = atomicCAS((unsigned long long*)&t.keys[h], (unsigned long long)EV_EMPTY, (unsigned long long)key);
-            if (k == EV_EMPTY) k = key;
-        }
-        if (k == key) {
-            unsigned long long* a = (unsigned long long*)&t.acc[4 * h];
-            atomicAdd(a, (unsigned long long)n);
-            atomicAdd(a + 1, (unsigned long long)sz);
-            atomicAdd(a + 2, (unsigned long long)sy);
-            atomicAdd(a + 3, (unsigned long long)sx);
-            u32 *lo = &t.lo[3 * h], *hi = &t.hi[3 * h];
-            atomicMin(lo, z0); atomicMin(lo + 1, y0); atomicMin(lo + 2, x0);
-            atomicMax(hi, z1); atomicMax(hi + 1, y1); atomicMax(hi + 2, x1);
-            return true;
-        }
-        h = (h + 1) & t.mask;
-    }
-    return false;
+    return tab_upsert(t.keys, t.mask, key, [&](u64 h) {
+        unsigned long long* a = (unsigned long long*)&t.acc[4 * h];
+        atomicAdd(a, (unsigned long long)n);
+        atomicAdd(a + 1, (unsigned long long)sz);
+        atomicAdd(a + 2, (unsigned long long)sy);
+        atomicAdd(a + 3, (unsigned long long)sx);
+        u32 *lo = &t.lo[3 * h], *hi = &t.hi[3 * h];
+        atomicMin(lo, z0); atomicMin(lo + 1, y0); atomicMin(lo + 2, x0);
+        atomicMax(hi, z1); atomicMax(hi + 1, y1); atomicMax(hi + 2, x1);
+    });
 }
 
 // Shaped like k_sf_count (contiguous voxel range per workgroup, boundaries by shuffle, run lengths
@@ -122,27 +107,16 @@ __global__ __launch_bounds__(RL_WG) void k_morph(const u64* __restrict__ lab, in
     const int64_t beg = (int64_t)blockIdx.x * per_wg, end = min(n, beg + per_wg);
     u32 e_or = 0;
     auto lds_add = [&](const MoAcc& a) {
-        u32 h = mo_lhash(a.key);
-#pragma unroll 1
-        for (int probe = 0; probe < EV_LDS_PROBES; ++probe) {
-            u64 k = lk[h];
-            if (k == EV_EMPTY) {
-                k = atomicCAS((unsigned long long*)&lk[h], (unsigned long long)EV_EMPTY, (unsigned long long)a.key);
-                if (k == EV_EMPTY) k = a.key;
-            }
-            if (k == a.key) {
-                atomicAdd(&ln[h], a.n);
-                atomicAdd((unsigned long long*)&ls[0][h], (unsigned long long)a.sz);
-                atomicAdd((unsigned long long*)&ls[1][h], (unsigned long long)a.sy);
-                atomicAdd((unsigned long long*)&ls[2][h], (unsigned long long)a.sx);
-                atomicMin(&lb[0][h], a.z0); atomicMin(&lb[1][h], a.y0); atomicMin(&lb[2][h], a.x0);
-                atomicMax(&lb[3][h], a.z1); atomicMax(&lb[4][h], a.y1); atomicMax(&lb[5][h], a.x1);
-                return;
-            }
-            h = (h + 1) & (MO_LDS - 1);
-        }
-        // LDS table crowded: straight to HBM
-        if (!mo_insert(tab, a.key, a.n, a.sz, a.sy, a.sx, a.z0, a.y0, a.x0, a.z1, a.y1, a.x1)) e_or |= EV_ERR_FULL;
+        lds_upsert<MO_LDS>(lk, lds_hash<MO_LDS_BITS>(a.key), a.key, [&](u32 h) {
+            atomicAdd(&ln[h], a.n);
+            atomicAdd((unsigned long long*)&ls[0][h], (unsigned long long)a.sz);
+            atomicAdd((unsigned long long*)&ls[1][h], (unsigned long long)a.sy);
+            atomicAdd((unsigned long long*)&ls[2][h], (unsigned long long)a.sx);
+            atomicMin(&lb[0][h], a.z0); atomicMin(&lb[1][h], a.y0); atomicMin(&lb[2][h], a.x0);
+            atomicMax(&lb[3][h], a.z1); atomicMax(&lb[4][h], a.y1); atomicMax(&lb[5][h], a.x1);
+        }, [&] {                                      // LDS table crowded: straight to HBM
+            if (!mo_insert(tab, a.key, a.n, a.sz, a.sy, a.sx, a.z0, a.y0, a.x0, a.z1, a.y1, a.x1)) e_or |= EV_ERR_FULL;
+        });
     };
     int64_t base = beg + (int64_t)(threadIdx.x & ~63) * RL_Q * VW;
     u32 zb, yb, xb;

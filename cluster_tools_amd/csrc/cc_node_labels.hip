@@ -186,84 +186,6 @@ static void nl_launch(cc_ctx* c, unsigned grid, const u64* ws, const void* label
     });
 }
 
-static int label_overlaps_impl(cc_ctx* c, const uint64_t* ws, const void* labels, int elem, const int64_t shape[3],
-                               const int64_t block_shape[3], int use_ignore, uint64_t ignore_label, uint64_t* n_out,
-                               uint64_t* ws_ids_host, uint64_t* label_ids_host, uint64_t* counts_host, int64_t host_cap) {
-    CC_REQUIRE(c && ws && labels && shape && block_shape && n_out && host_cap >= 0, "bad arguments");
-    CC_REQUIRE(elem == 1 || elem == 2 || elem == 4 || elem == 8, "label_elem_size must be 1, 2, 4 or 8");
-    const bool want = ws_ids_host || label_ids_host || counts_host;
-    CC_REQUIRE(!want || (ws_ids_host && label_ids_host && counts_host), "the three host arrays go together");
-    HIP_OK(hipSetDevice(c->device));
-    hipStream_t s = cstream(c);
-    c->nl_n = -1;
-    int64_t nb[3];
-    for (int a = 0; a < 3; ++a) {
-        CC_REQUIRE(shape[a] >= 1 && block_shape[a] >= 1, "shape and block_shape must be >= 1");
-        CC_REQUIRE(shape[a] < (1LL << 31), "every dimension must be below 2^31");
-        nb[a] = (shape[a] + block_shape[a] - 1) / block_shape[a];
-    }
-    const unsigned __int128 nblk = (unsigned __int128)((u64)nb[0] * (u64)nb[1]) * (u64)nb[2];
-    CC_REQUIRE(nblk < ((unsigned __int128)1 << 31), "too many blocks (>= 2^31)");
-    const int64_t n_blocks = (int64_t)nblk;
-    CC_REQUIRE(((uintptr_t)ws & 7) == 0, "ws must be 8-byte aligned");
-    CC_REQUIRE(((uintptr_t)labels & (uintptr_t)(elem - 1)) == 0, "labels must be aligned to their element size");
-    EvGrid gr{shape[1], shape[2], block_shape[0], block_shape[1], block_shape[2], nb[1], nb[2]};
-    // rows of one workgroup: ~8192 workgroups on large volumes (cc_evaluate's geometry)
-    const int64_t n_rows = shape[0] * shape[1];
-    const int64_t rows_per_wg = std::max<int64_t>(1, (n_rows + 8191) / 8192);
-    const unsigned grid = (unsigned)((n_rows + rows_per_wg - 1) / rows_per_wg);
-    c->nl_flag.ensure(n_blocks * sizeof(u32) + 16);
-    int64_t n = 0;
-    u64* comp = nullptr;
-    // keep the table at most half full (linear probing); grow and rerun otherwise
-    const int64_t cap = table_pass(c->nl_cap, 1 << 16, host_cap, "overlap table larger than 2^30 pairs", [&](int64_t cap) {
-        c->nl_tab.ensure(4 * cap * sizeof(u64));       // pair keys | counts | ws-0 keys | counts
-        c->nl_comp.ensure(2 * cap * sizeof(u64));      // compacted keys | counts
-        u64* mk = c->nl_tab.as<u64>();
-        u64* zk = mk + 2 * cap;
-        comp = c->nl_comp.as<u64>();
-        for (u64* k : {mk, zk}) table_clear(c, k, cap * sizeof(u64), cap * sizeof(u64));
-        HIP_OK(hipMemsetAsync(c->nl_flag.p, 0, n_blocks * sizeof(u32), s));
-        u32* err = counters_clear(c, 2);
-        EvTabs t{mk, mk + cap, zk, zk + cap, (u64)cap - 1, err};
-        u32* flag = c->nl_flag.as<u32>();
-        const int ui = use_ignore ? 1 : 0;
-        switch (elem) {
-            case 1: nl_launch<uint8_t>(c, grid, ws, labels, n_rows, rows_per_wg, gr, ui, ignore_label, t, flag); break;
-            case 2: nl_launch<uint16_t>(c, grid, ws, labels, n_rows, rows_per_wg, gr, ui, ignore_label, t, flag); break;
-            case 4: nl_launch<uint32_t>(c, grid, ws, labels, n_rows, rows_per_wg, gr, ui, ignore_label, t, flag); break;
-            default: nl_launch<u64>(c, grid, ws, labels, n_rows, rows_per_wg, gr, ui, ignore_label, t, flag); break;
-        }
-        launch(c, "k_ev_fold", [&] { k_ev_fold<<<grid_stride(cap), 256, 0, s>>>(t, flag); });
-        // (the kernel is k_tab_compact; the profile keeps this pass's own name for it)
-        launch(c, "k_nl_compact", [&] { k_tab_compact<<<grid_stride(cap), 256, 0, s>>>(mk, mk + cap, (u64)cap, comp, comp + cap, err + 1); });
-        u32 h[2] = {0, 0};
-        counters_read(c, h);
-        if (h[0] & EV_ERR_SEG) throw CCIdRangeError{{"ws id >= 2^31 (overlap keys pack ws ids in 31 bits)"}};
-        if (h[0] & EV_ERR_GT) throw CCIdRangeError{{"label id >= 2^32 - 1 (overlap keys pack label ids in 32 bits)"}};
-        n = h[1];
-        return TableFill{(h[0] & EV_ERR_FULL) != 0, n};
-    });
-    // sorted keys | ws ids | label ids | counts: the triples stay here for cc_max_overlaps
-    c->nl_sorted.ensure((size_t)(4 * n + 4) * sizeof(u64));
-    u64* skey = c->nl_sorted.as<u64>();
-    u64* wid = skey + n + 1;
-    u64* lid = wid + n + 1;
-    u64* cnt = lid + n + 1;
-    if (n) {
-        launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp, skey, comp + cap, cnt, n, 0, 64, c->cub_tmp, s); });
-        launch(c, "k_nl_unpack", [&] { k_nl_unpack<<<grid1d(n), 256, 0, s>>>(skey, n, wid, lid); });
-    }
-    c->nl_n = n;
-    *n_out = (uint64_t)n;
-    if (want && n && n <= host_cap) {
-        HIP_OK(hipMemcpyAsync(ws_ids_host, wid, n * sizeof(u64), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(label_ids_host, lid, n * sizeof(u64), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(counts_host, cnt, n * sizeof(u64), hipMemcpyDeviceToHost, s));
-    }
-    sync(c);
-    return 0;
-}
 
 static void max_overlaps_impl(cc_ctx* c, const uint64_t* ws_ids, const uint64_t* label_ids, const uint64_t* counts, int64_t n,
                               uint64_t number_of_labels, uint64_t* out_labels_host, uint64_t* out_counts_host) {
@@ -303,22 +225,84 @@ static void max_overlaps_impl(cc_ctx* c, const uint64_t* ws_ids, const uint64_t*
 
 extern "C" {
 
-int cc_label_overlaps(cc_ctx* c, const uint64_t* ws, const void* labels, int label_elem_size, const int64_t shape[3],
-                      const int64_t block_shape[3], int use_ignore, uint64_t ignore_label, uint64_t* n,
-                      uint64_t* ws_ids_host, uint64_t* label_ids_host, uint64_t* counts_host, int64_t cap) {
-    try {
-        return label_overlaps_impl(c, ws, labels, label_elem_size, shape, block_shape, use_ignore, ignore_label, n,
-                                   ws_ids_host, label_ids_host, counts_host, cap);
-    } catch (const CCIdRangeError& e) {
-        g_err = e.msg;
-        return CC_ERR_ID_RANGE;
-    } catch (const CCError& e) {
-        g_err = e.msg;
-        return -1;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return -2;
-    }
+int cc_label_overlaps(cc_ctx* c, const uint64_t* ws, const void* labels, int elem, const int64_t shape[3],
+                      const int64_t block_shape[3], int use_ignore, uint64_t ignore_label, uint64_t* n_out,
+                      uint64_t* ws_ids_host, uint64_t* label_ids_host, uint64_t* counts_host, int64_t host_cap) {
+    CC_TRY({
+        CC_REQUIRE(c && ws && labels && shape && block_shape && n_out && host_cap >= 0, "bad arguments");
+        CC_REQUIRE(elem == 1 || elem == 2 || elem == 4 || elem == 8, "label_elem_size must be 1, 2, 4 or 8");
+        const bool want = ws_ids_host || label_ids_host || counts_host;
+        CC_REQUIRE(!want || (ws_ids_host && label_ids_host && counts_host), "the three host arrays go together");
+        HIP_OK(hipSetDevice(c->device));
+        hipStream_t s = cstream(c);
+        c->nl_n = -1;
+        int64_t nb[3];
+        for (int a = 0; a < 3; ++a) {
+            CC_REQUIRE(shape[a] >= 1 && block_shape[a] >= 1, "shape and block_shape must be >= 1");
+            CC_REQUIRE(shape[a] < (1LL << 31), "every dimension must be below 2^31");
+            nb[a] = (shape[a] + block_shape[a] - 1) / block_shape[a];
+        }
+        const unsigned __int128 nblk = (unsigned __int128)((u64)nb[0] * (u64)nb[1]) * (u64)nb[2];
+        CC_REQUIRE(nblk < ((unsigned __int128)1 << 31), "too many blocks (>= 2^31)");
+        const int64_t n_blocks = (int64_t)nblk;
+        CC_REQUIRE(((uintptr_t)ws & 7) == 0, "ws must be 8-byte aligned");
+        CC_REQUIRE(((uintptr_t)labels & (uintptr_t)(elem - 1)) == 0, "labels must be aligned to their element size");
+        EvGrid gr{shape[1], shape[2], block_shape[0], block_shape[1], block_shape[2], nb[1], nb[2]};
+        // rows of one workgroup: ~8192 workgroups on large volumes (cc_evaluate's geometry)
+        const int64_t n_rows = shape[0] * shape[1];
+        const int64_t rows_per_wg = std::max<int64_t>(1, (n_rows + 8191) / 8192);
+        const unsigned grid = (unsigned)((n_rows + rows_per_wg - 1) / rows_per_wg);
+        c->nl_flag.ensure(n_blocks * sizeof(u32) + 16);
+        int64_t n = 0;
+        u64* comp = nullptr;
+        // keep the table at most half full (linear probing); grow and rerun otherwise
+        const int64_t cap = table_pass(c->nl_cap, 1 << 16, host_cap, "overlap table larger than 2^30 pairs", [&](int64_t cap) {
+            c->nl_tab.ensure(4 * cap * sizeof(u64));       // pair keys | counts | ws-0 keys | counts
+            c->nl_comp.ensure(2 * cap * sizeof(u64));      // compacted keys | counts
+            u64* mk = c->nl_tab.as<u64>();
+            u64* zk = mk + 2 * cap;
+            comp = c->nl_comp.as<u64>();
+            for (u64* k : {mk, zk}) table_clear(c, k, cap * sizeof(u64), cap * sizeof(u64));
+            HIP_OK(hipMemsetAsync(c->nl_flag.p, 0, n_blocks * sizeof(u32), s));
+            u32* err = counters_clear(c, 2);
+            EvTabs t{mk, mk + cap, zk, zk + cap, (u64)cap - 1, err};
+            u32* flag = c->nl_flag.as<u32>();
+            const int ui = use_ignore ? 1 : 0;
+            switch (elem) {
+                case 1: nl_launch<uint8_t>(c, grid, ws, labels, n_rows, rows_per_wg, gr, ui, ignore_label, t, flag); break;
+                case 2: nl_launch<uint16_t>(c, grid, ws, labels, n_rows, rows_per_wg, gr, ui, ignore_label, t, flag); break;
+                case 4: nl_launch<uint32_t>(c, grid, ws, labels, n_rows, rows_per_wg, gr, ui, ignore_label, t, flag); break;
+                default: nl_launch<u64>(c, grid, ws, labels, n_rows, rows_per_wg, gr, ui, ignore_label, t, flag); break;
+            }
+            launch(c, "k_ev_fold", [&] { k_ev_fold<<<grid_stride(cap), 256, 0, s>>>(t, flag); });
+            // (the kernel is k_tab_compact; the profile keeps this pass's own name for it)
+            launch(c, "k_nl_compact", [&] { k_tab_compact<<<grid_stride(cap), 256, 0, s>>>(mk, mk + cap, (u64)cap, comp, comp + cap, err + 1); });
+            u32 h[2] = {0, 0};
+            counters_read(c, h);
+            if (h[0] & EV_ERR_SEG) throw CCIdRangeError{{"ws id >= 2^31 (overlap keys pack ws ids in 31 bits)"}};
+            if (h[0] & EV_ERR_GT) throw CCIdRangeError{{"label id >= 2^32 - 1 (overlap keys pack label ids in 32 bits)"}};
+            n = h[1];
+            return TableFill{(h[0] & EV_ERR_FULL) != 0, n};
+        });
+        // sorted keys | ws ids | label ids | counts: the triples stay here for cc_max_overlaps
+        c->nl_sorted.ensure((size_t)(4 * n + 4) * sizeof(u64));
+        u64* skey = c->nl_sorted.as<u64>();
+        u64* wid = skey + n + 1;
+        u64* lid = wid + n + 1;
+        u64* cnt = lid + n + 1;
+        if (n) {
+            launch(c, "radix_sort", [&] { prims::sort_pairs<u64, u64>(comp, skey, comp + cap, cnt, n, 0, 64, c->cub_tmp, s); });
+            launch(c, "k_nl_unpack", [&] { k_nl_unpack<<<grid1d(n), 256, 0, s>>>(skey, n, wid, lid); });
+        }
+        c->nl_n = n;
+        *n_out = (uint64_t)n;
+        if (want && n && n <= host_cap) {
+            HIP_OK(hipMemcpyAsync(ws_ids_host, wid, n * sizeof(u64), hipMemcpyDeviceToHost, s));
+            HIP_OK(hipMemcpyAsync(label_ids_host, lid, n * sizeof(u64), hipMemcpyDeviceToHost, s));
+            HIP_OK(hipMemcpyAsync(counts_host, cnt, n * sizeof(u64), hipMemcpyDeviceToHost, s));
+        }
+        sync(c);
+    })
 }
 
 int cc_max_overlaps(cc_ctx* c, const uint64_t* ws_ids, const uint64_t* label_ids, const uint64_t* counts, int64_t n,

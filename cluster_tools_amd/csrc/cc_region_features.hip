@@ -83,26 +83,15 @@ __device__ __forceinline__ void rf_gadd(u64* p, double v) { unsafeAtomicAdd(rein
 __device__ __forceinline__ void rf_ladd(u64* p, u64 v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
 __device__ __forceinline__ void rf_ladd(u64* p, double v) { atomicAdd(reinterpret_cast<double*>(p), v); }
 
-// global open-addressing update (linear probing, as ev_insert); false when EV_PROBES slots were taken
+// update of an id's record in the HBM table (tab_upsert); false when the table is full
 template <typename A>
 __device__ bool rf_insert(const RfTab& t, u64 key, u64 n, A sum, u32 kmn, u32 kmx) {
-    u64 h = ev_hash(key) & t.mask;
-    for (int probe = 0; probe < EV_PROBES; ++probe) {
-        u64 k = __hip_atomic_load(&t.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == EV_EMPTY) {
-            k = atomicCAS((unsigned long long*)&t.keys[h], (unsigned long long)EV_EMPTY, (unsigned long long)key);
-            if (k == EV_EMPTY) k = key;
-        }
-        if (k == key) {
-            atomicAdd((unsigned long long*)&t.cnt[h], (unsigned long long)n);
-            rf_gadd(&t.sum[h], sum);
-            atomicMin(&t.kmn[h], kmn);
-            atomicMax(&t.kmx[h], kmx);
-            return true;
-        }
-        h = (h + 1) & t.mask;
-    }
-    return false;
+    return tab_upsert(t.keys, t.mask, key, [&](u64 h) {
+        atomicAdd((unsigned long long*)&t.cnt[h], (unsigned long long)n);
+        rf_gadd(&t.sum[h], sum);
+        atomicMin(&t.kmn[h], kmn);
+        atomicMax(&t.kmx[h], kmx);
+    });
 }
 
 template <typename T>
@@ -145,25 +134,14 @@ __global__ __launch_bounds__(RL_WG) void k_rf(const u64* __restrict__ lab, const
     const int64_t beg = (int64_t)blockIdx.x * per_wg, end = min(n, beg + per_wg);
     u32 e_or = 0;
     auto lds_add = [&](u64 key, u32 c, acc_t s, u32 mn, u32 mx) {
-        u32 h = rl_lhash(key);
-#pragma unroll 1
-        for (int probe = 0; probe < EV_LDS_PROBES; ++probe) {
-            u64 k = lk[h];
-            if (k == EV_EMPTY) {
-                k = atomicCAS((unsigned long long*)&lk[h], (unsigned long long)EV_EMPTY, (unsigned long long)key);
-                if (k == EV_EMPTY) k = key;
-            }
-            if (k == key) {
-                atomicAdd(&lc[h], c);
-                rf_ladd(&ls[h], s);
-                atomicMin(&lmn[h], mn);
-                atomicMax(&lmx[h], mx);
-                return;
-            }
-            h = (h + 1) & (EV_LDS - 1);
-        }
-        // LDS table crowded: straight to HBM
-        if (!rf_insert(tab, key, (u64)c, s, mn, mx)) e_or |= EV_ERR_FULL;
+        lds_upsert<EV_LDS>(lk, lds_hash<RL_LDS_BITS>(key), key, [&](u32 h) {
+            atomicAdd(&lc[h], c);
+            rf_ladd(&ls[h], s);
+            atomicMin(&lmn[h], mn);
+            atomicMax(&lmx[h], mx);
+        }, [&] {                                      // LDS table crowded: straight to HBM
+            if (!rf_insert(tab, key, (u64)c, s, mn, mx)) e_or |= EV_ERR_FULL;
+        });
     };
     // this lane's last two ids and their records (runs alternate)
     u64 r0 = EV_EMPTY, r1 = EV_EMPTY;

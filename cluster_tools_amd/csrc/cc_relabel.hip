@@ -12,16 +12,6 @@
 
 namespace cc {
 
-__device__ __forceinline__ u64 rl_slot(const u64* keys, u64 mask, u64 key) {
-    u64 h = ev_hash(key) & mask;
-    for (int probe = 0; probe < EV_PROBES; ++probe) {
-        const u64 k = keys[h];
-        if (k == key || k == EV_EMPTY) return h;
-        h = (h + 1) & mask;
-    }
-    return ~0ull;
-}
-
 constexpr int RL_Q = 8;      // loads per lane per wave iteration (RL_Q * VW voxels in flight)
 #ifndef CC_RL_QA
 #define CC_RL_QA 8
@@ -32,20 +22,9 @@ typedef unsigned long long rl_u64x2 __attribute__((ext_vector_type(2)));
 constexpr int RL_LDS_BITS = 11;
 static_assert((1 << RL_LDS_BITS) == EV_LDS, "LDS set size");
 
-// slot of an id in a workgroup's LDS set (any hash will do: the set is private to the kernel)
-__device__ __forceinline__ u32 rl_lhash(u64 k) {
-    return ((u32)k ^ (u32)(k >> 32) * 0x85EBCA6Bu) * 0x9E3779B1u >> (32 - RL_LDS_BITS);
-}
-
-// global set insert; false when EV_PROBES slots were taken
+// global set insert (tab_upsert, a CAS on every probe); false when the set is full
 __device__ __forceinline__ bool rl_insert(u64* keys, u64 mask, u64 key) {
-    u64 h = ev_hash(key) & mask;
-    for (int probe = 0; probe < EV_PROBES; ++probe) {
-        u64 k = atomicCAS((unsigned long long*)&keys[h], (unsigned long long)EV_EMPTY, (unsigned long long)key);
-        if (k == EV_EMPTY || k == key) return true;
-        h = (h + 1) & mask;
-    }
-    return false;
+    return tab_upsert<false>(keys, mask, key, [](u64) {});
 }
 
 // VW consecutive ids per lane (one 8 VW-byte load), run heads: a voxel whose left neighbour
@@ -119,7 +98,9 @@ __global__ __launch_bounds__(RL_WG) void k_rl_unique(const u64* __restrict__ lab
     auto head = [&](u64 key) {
         if (key == r0 || key == r1) return;
         r1 = r0; r0 = key;
-        u32 h = rl_lhash(key);
+        // (hand-written, not lds_upsert: only a won CAS sends the id on, and a helper that tells
+        // won from found compiled to other code here)
+        u32 h = lds_hash<RL_LDS_BITS>(key);
         int probe = 0;
 #pragma unroll 1
         for (; probe < EV_LDS_PROBES; ++probe) {
@@ -170,7 +151,7 @@ __global__ __launch_bounds__(256) void k_rl_assign(const u64* __restrict__ sorte
                                                    const u64* __restrict__ keys, u64 mask, u64* vals) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nu) return;
-    vals[rl_slot(keys, mask, sorted[i])] = (u64)i + start;
+    vals[tab_find(keys, mask, sorted[i])] = (u64)i + start;
 }
 
 // out[i] = new id of lab[i] over k_rl_unique's workgroup ranges: the workgroup's id list -> LDS
@@ -189,8 +170,8 @@ __global__ __launch_bounds__(RL_WG) void k_rl_apply(const u64* lab, int64_t n, i
     if (!global) {
         for (u32 e = threadIdx.x; e < nl; e += RL_WG) {
             const u64 key = WGL[(int64_t)blockIdx.x * EV_LDS + e];
-            const u64 val = vals[rl_slot(keys, mask, key)];
-            u32 h = rl_lhash(key);
+            const u64 val = vals[tab_find(keys, mask, key)];
+            u32 h = lds_hash<RL_LDS_BITS>(key);
             while (atomicCAS((unsigned long long*)&lk[h], (unsigned long long)EV_EMPTY, (unsigned long long)key) != EV_EMPTY)
                 h = (h + 1) & (EV_LDS - 1);       // the ids are distinct and nl <= EV_LDS
             lv[h] = val;
@@ -203,15 +184,15 @@ __global__ __launch_bounds__(RL_WG) void k_rl_apply(const u64* lab, int64_t n, i
         if (key == mk1) return mv1;
         u64 v = 0;
         if (global) {
-            v = vals[rl_slot(keys, mask, key)];
+            v = vals[tab_find(keys, mask, key)];
         } else {
-            u32 h = rl_lhash(key);
+            u32 h = lds_hash<RL_LDS_BITS>(key);
             int probe = 0;
             for (; probe < EV_LDS; ++probe) {        // always found: the list holds every id of the range
                 if (lk[h] == key) break;
                 h = (h + 1) & (EV_LDS - 1);
             }
-            v = probe < EV_LDS ? lv[h] : vals[rl_slot(keys, mask, key)];
+            v = probe < EV_LDS ? lv[h] : vals[tab_find(keys, mask, key)];
         }
         mk1 = mk0; mv1 = mv0; mk0 = key; mv0 = v;
         return v;

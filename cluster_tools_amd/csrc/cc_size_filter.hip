@@ -81,22 +81,10 @@ __global__ __launch_bounds__(RL_WG) void k_sf_count(const u64* __restrict__ lab,
     const int64_t beg = (int64_t)blockIdx.x * per_wg, end = min(n, beg + per_wg);
     u32 e_or = 0, ovf = 0;
     auto lds_add = [&](u64 key, u32 c) {
-        u32 h = rl_lhash(key);
-#pragma unroll 1
-        for (int probe = 0; probe < EV_LDS_PROBES; ++probe) {
-            u64 k = lk[h];
-            if (k == EV_EMPTY) {
-                k = atomicCAS((unsigned long long*)&lk[h], (unsigned long long)EV_EMPTY, (unsigned long long)key);
-                if (k == EV_EMPTY) k = key;
-            }
-            if (k == key) {
-                atomicAdd(&lc[h], c);
-                return;
-            }
-            h = (h + 1) & (EV_LDS - 1);
-        }
-        ovf = 1;                                      // LDS table crowded: straight to HBM
-        if (!ev_insert(keys, cnts, mask, key, (u64)c)) e_or |= EV_ERR_FULL;
+        lds_upsert<EV_LDS>(lk, lds_hash<RL_LDS_BITS>(key), key, [&](u32 h) { atomicAdd(&lc[h], c); }, [&] {
+            ovf = 1;                                  // LDS table crowded: straight to HBM
+            if (!ev_insert(keys, cnts, mask, key, (u64)c)) e_or |= EV_ERR_FULL;
+        });
     };
     u64 r0 = EV_EMPTY, r1 = EV_EMPTY;                 // this lane's last two ids and their counts
     u32 c0 = 0, c1 = 0;
@@ -202,7 +190,7 @@ __global__ __launch_bounds__(256) void k_sf_assign(const u64* __restrict__ ids, 
         } else if (id != 0) {
             gone = counts[i];
         }
-        vals[rl_slot(keys, mask, id)] = v;
+        vals[tab_find(keys, mask, id)] = v;
         new_ids[i] = v;
     }
 #pragma unroll
