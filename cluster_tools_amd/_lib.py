@@ -33,6 +33,7 @@ EXPORTS = (
     'cc_label_sizes', 'cc_size_filter', 'cc_morphology', 'cc_region_features',
     'cc_region_graph', 'cc_edge_features', 'cc_label_overlaps', 'cc_max_overlaps', 'cc_affinity_features',
     'cc_distance_transform', 'cc_gaussian_smooth_domains', 'cc_local_maxima_seeds',
+    'cc_watershed_height_map', 'cc_watershed_domains',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -176,6 +177,8 @@ def load(host_only=False):
         'cc_distance_transform': (I, [P, P, P, P, I, P, I, P]),
         'cc_gaussian_smooth_domains': (I, [P, P, P, P, I, ctypes.c_double, P]),
         'cc_local_maxima_seeds': (I, [P, P, P, P, I, P, P]),
+        'cc_watershed_height_map': (I, [P, P, P, P, P, I, ctypes.c_double, ctypes.c_double, P]),
+        'cc_watershed_domains': (I, [P, P, P, P, P, P, P, I, ctypes.c_int64, P, P, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -1037,6 +1040,99 @@ class Context:
         if apply_2d:
             return self.local_maxima_seeds(x, (1, by, bx), indirect=True, return_counts=True)
         return self.local_maxima_seeds(x, block_shape, indirect=False, return_counts=True)
+
+    def normalized_input(self, inp, block_shape, agglomerate='mean', invert=False, mask=None):
+        """The watershed tasks' input_ (_read_data + _ws_block, watershed.py:268-304) on device:
+        inp is the float32 CUDA input (Z, Y, X) or its selected channels (C, Z, Y, X); normalized
+        per block (normalize_channels; one channel: its maximum over the channels is itself),
+        1 - x when invert, 1 where the uint8 mask is 0.  Returns a new (Z, Y, X) float32 tensor."""
+        xn = (self.normalize_channels(inp, block_shape, agglomerate) if inp.dim() == 4
+              else self.normalize_channels(inp[None], block_shape, 'max'))
+        if invert:
+            xn = 1. - xn
+        if mask is not None:
+            xn[mask == 0] = 1
+        return xn
+
+    def watershed_height_map(self, inp, dt, block_shape, alpha=.8, sigma_weights=2., apply_2d=True, out=None):
+        """_make_hmap (watershed.py:164-170) on device, per block (apply_2d: per z-slice of each
+        block): alpha * inp + (1 - alpha) * (1 - normalize(dt)) in float32 as numpy rounds it,
+        then gaussian_smooth_domains' filter unless sigma_weights is 0.  inp (normalized_input's
+        result) and dt are float32 CUDA volumes; out may be inp.  See include/cc_mi355x.h."""
+        import torch
+        for t in (inp, dt):
+            assert hasattr(t, 'data_ptr') and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        assert inp.dim() == 3 and dt.shape == inp.shape
+        shape, bs = _i64(inp.shape), _i64(block_shape)
+        assert len(bs) == 3
+        if out is None:
+            out = torch.empty_like(inp)
+        assert out.is_cuda and out.dtype == torch.float32 and out.shape == inp.shape and out.is_contiguous()
+        _check(load().cc_watershed_height_map(self._h, _ptr(inp), _ptr(dt), _ptr(shape), _ptr(bs), int(bool(apply_2d)),
+                                              float(alpha), float(sigma_weights or 0.), _ptr(out)))
+        return out
+
+    def watershed_domains(self, values, seeds, counts, block_shape, mask=None, apply_2d=True, size_filter=0,
+                          out=None, return_rounds=False):
+        """run_watershed of _apply_watershed (watershed.py:212-250) on device: the seeds
+        (local_maxima_seeds' result: ids 1 .. counts[d] per domain, torch int64) grow over the
+        float32 values as they are, per block or (apply_2d) per z-slice of each block; labels of
+        fewer than size_filter voxels are removed and the rest grown again; the output is 0 outside
+        the uint8 mask.  out may be `seeds`.  Returns (labels, max_ids) -- max_ids[d] the largest
+        in-mask label of domain d (int64) -- and with return_rounds the relaxation rounds of the two
+        watersheds.  See include/cc_mi355x.h."""
+        import torch
+        assert hasattr(values, 'data_ptr') and values.is_cuda and values.dtype == torch.float32
+        assert values.dim() == 3 and values.is_contiguous()
+        assert seeds.is_cuda and seeds.element_size() == 8 and seeds.shape == values.shape and seeds.is_contiguous()
+        assert counts.is_cuda and counts.element_size() == 8 and counts.dim() == 1 and counts.is_contiguous()
+        if mask is not None:
+            assert mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == values.shape and mask.is_contiguous()
+        shape, bs = _i64(values.shape), _i64(block_shape)
+        assert len(bs) == 3 and all(int(b) > 0 for b in bs)
+        nd = 1
+        for a, (s, b) in enumerate(zip(shape, bs)):
+            d = 1 if (a == 0 and apply_2d) else min(int(b), int(s))
+            nd *= 0 if s == 0 else -(-int(s) // d)
+        assert counts.numel() == nd, 'one count per domain'
+        if out is None:
+            out = torch.empty(tuple(values.shape), dtype=torch.int64, device=values.device)
+        assert out.is_cuda and out.element_size() == 8 and out.shape == values.shape and out.is_contiguous()
+        max_ids = torch.zeros(nd, dtype=torch.int64, device=values.device)
+        rounds = np.zeros(2, dtype=np.int64)
+        _check(load().cc_watershed_domains(self._h, _ptr(values), _ptr(seeds), _ptr(counts), _ptr(mask), _ptr(shape),
+                                           _ptr(bs), int(bool(apply_2d)), int(size_filter), _ptr(out), _ptr(max_ids),
+                                           _ptr(rounds)))
+        return (out, max_ids, (int(rounds[0]), int(rounds[1]))) if return_rounds else (out, max_ids)
+
+    def dt_watershed(self, input_, block_shape, mask=None, return_objects=False, **config):
+        """The reference's distance-transform watershed of a block (_ws_block, watershed.py:286-344,
+        without halo) over every block of the volume, on device tensors: normalized_input
+        (agglomerate_channels, invert_inputs), the objects `> threshold` and their
+        distance_transform (apply_dt_2d, pixel_pitch), watershed_seeds (sigma_seeds, apply_ws_2d),
+        watershed_height_map (alpha, sigma_weights) and watershed_domains (size_filter).  input_ is
+        the float32 CUDA input (Z, Y, X) or its selected channels (C, Z, Y, X); the config keys and
+        their defaults are the reference task's (:54-60).  Returns (labels local to each domain,
+        max_ids per domain), with return_objects also the uint8 object mask (a block without an
+        object voxel is the task's constant block)."""
+        import torch
+        known = ('threshold', 'apply_dt_2d', 'pixel_pitch', 'apply_ws_2d', 'sigma_seeds', 'size_filter',
+                 'sigma_weights', 'agglomerate_channels', 'alpha', 'invert_inputs')
+        assert all(k in known for k in config), 'unknown key in %s' % sorted(config)
+        ws_2d = bool(config.get('apply_ws_2d', True))
+        xn = self.normalized_input(input_, block_shape, config.get('agglomerate_channels', 'mean'),
+                                   bool(config.get('invert_inputs', False)), mask)
+        # a float32 compare, as numpy's of a float32 array with a python float
+        thr = torch.tensor(float(np.float32(config.get('threshold', .5))), dtype=torch.float32, device=xn.device)
+        obj = (xn > thr).to(torch.uint8)
+        dt = self.distance_transform(obj, block_shape, apply_2d=bool(config.get('apply_dt_2d', True)),
+                                     pixel_pitch=config.get('pixel_pitch', None))
+        seeds, counts = self.watershed_seeds(dt, block_shape, config.get('sigma_seeds', 2.), apply_2d=ws_2d)
+        hmap = self.watershed_height_map(xn, dt, block_shape, config.get('alpha', .8), config.get('sigma_weights', 2.),
+                                         apply_2d=ws_2d, out=xn)
+        labels, max_ids = self.watershed_domains(hmap, seeds, counts, block_shape, mask, apply_2d=ws_2d,
+                                                 size_filter=config.get('size_filter', 25), out=seeds)
+        return (labels, max_ids, obj) if return_objects else (labels, max_ids)
 
     def evaluate(self, seg, gt, block_shape, ignore_label=0):
         """EvaluationWorkflow (evaluation/evaluation_workflow.py:46-84) on device: overlaps per

@@ -505,6 +505,23 @@ static void gauss_passes(cc_ctx* c, const float* in, float* out, const int64_t s
     }
 }
 
+// the argument checks of cc_gaussian_smooth_domains (and of the height map's smoothing,
+// cc_dt_watershed.hip), and the taps of sigma
+static void gauss_domain_taps(const int64_t shape[3], const int64_t block_shape[3], int apply_2d, double sigma,
+                              GaussTaps& tp) {
+    CC_REQUIRE(sigma > 0, "sigma must be > 0");
+    const int r = gauss_taps(sigma, tp);
+    CC_REQUIRE(r > 0, "sigma too large (kernel radius > 64)");
+    for (int a = 0; a < 3; ++a) {
+        CC_REQUIRE(shape[a] >= 1 && block_shape[a] >= 1, "bad shape / block_shape");
+        CC_REQUIRE(shape[a] < (1ll << 31), "axis too long");
+        if (a == 0 && apply_2d) continue;
+        const int64_t last = shape[a] - (shape[a] - 1) / block_shape[a] * block_shape[a];
+        CC_REQUIRE(std::min(block_shape[a], shape[a]) > r && last > r,
+                   "gaussian_smooth_domains: kernel longer than a block line (block extent <= 3 sigma)");
+    }
+}
+
 }  // namespace cc
 
 extern "C" {
@@ -566,18 +583,8 @@ int cc_gaussian_smooth_domains(cc_ctx* c, const float* in, const int64_t shape[3
                                int apply_2d, double sigma, float* out) {
     CC_TRY({
         CC_REQUIRE(c && in && out && shape && block_shape, "NULL argument");
-        CC_REQUIRE(sigma > 0, "sigma must be > 0");
         GaussTaps tp;
-        const int r = gauss_taps(sigma, tp);
-        CC_REQUIRE(r > 0, "sigma too large (kernel radius > 64)");
-        for (int a = 0; a < 3; ++a) {
-            CC_REQUIRE(shape[a] >= 1 && block_shape[a] >= 1, "bad shape / block_shape");
-            CC_REQUIRE(shape[a] < (1ll << 31), "axis too long");
-            if (a == 0 && apply_2d) continue;
-            const int64_t last = shape[a] - (shape[a] - 1) / block_shape[a] * block_shape[a];
-            CC_REQUIRE(std::min(block_shape[a], shape[a]) > r && last > r,
-                       "gaussian_smooth_domains: kernel longer than a block line (block extent <= 3 sigma)");
-        }
+        gauss_domain_taps(shape, block_shape, apply_2d, sigma, tp);
         HIP_OK(hipSetDevice(c->device));
         gauss_passes(c, in, out, shape, block_shape, tp, false, apply_2d != 0, 0, nullptr, nullptr, nullptr);
         sync(c);

@@ -20,6 +20,11 @@
 // given the halo (voxel-by-voxel sweeps), rounds of launches over the tiles whose neighbours
 // changed until none changes (phase 1: costs; phase 2: labels on the converged costs).  Every
 // round after a phase's first visits only the tiles the previous round listed.
+//
+// The kernels are templates over the tile geometry (WsShape): WsCube is that 8 x 8 x 32 tile;
+// WsFlat, one z-slice of 32 x 64 voxels with a halo in y and x only and four neighbours, serves the
+// per-slice domains of cc_watershed_domains (cc_dt_watershed.hip), where a cube tile would hold
+// one eighth of its voxels.
 namespace cc {
 
 // tile shape and threads (CC_WS_TZ / TY / TX / TT at build time, each on its own: A/B only)
@@ -35,16 +40,43 @@ namespace cc {
 #ifndef CC_WS_TT
 #define CC_WS_TT 256
 #endif
-constexpr int WS_Z = CC_WS_TZ, WS_Y = CC_WS_TY, WS_X = CC_WS_TX, WS_T = CC_WS_TT;
-static_assert(WS_Z * WS_Y * WS_X % WS_T == 0, "whole voxels per thread");
-static_assert(WS_T % 64 == 0 && WS_T >= 64, "whole waves per tile");
-static_assert(WS_T >= 6, "ws_list_neighbours lists the six face neighbours with one thread each");
+// the flat tile of the per-slice watershed (cc_watershed_domains with apply_2d): 1 x FY x FX voxels,
+// FT threads; 32 x 64 with 256 threads is the fastest of the eight shapes and three thread counts
+// measured
+#ifndef CC_WS_FY
+#define CC_WS_FY 32
+#endif
+#ifndef CC_WS_FX
+#define CC_WS_FX 64
+#endif
+#ifndef CC_WS_FT
+#define CC_WS_FT 256
+#endif
 #ifndef CC_WS_ALT
 #define CC_WS_ALT 0        // A/B only: odd sweeps walk a thread's voxels in reverse order
 #endif
-constexpr int WS_HZ = WS_Z + 2, WS_HY = WS_Y + 2, WS_HX = WS_X + 2, WS_HN = WS_HZ * WS_HY * WS_HX;
-constexpr int WS_VPT = WS_Z * WS_Y * WS_X / WS_T;      // interior voxels per thread
 constexpr u32 WS_INF = 0xFFFFFFFFu;
+
+// A tile geometry.  FLAT: the tile is one z-slice of a slice domain: no z halo, and of the six
+// neighbours (-z, +z, -y, +y, -x, +x) only the last four exist.
+template <int Z_, int Y_, int X_, int T_, bool FLAT_>
+struct WsShape {
+    static constexpr int Z = Z_, Y = Y_, X = X_, T = T_, N = Z_ * Y_ * X_;
+    static constexpr bool FLAT = FLAT_;
+    static constexpr int HZ = FLAT_ ? 1 : Z_ + 2, HY = Y_ + 2, HX = X_ + 2, HN = HZ * HY * HX;
+    static constexpr int OZ = FLAT_ ? 0 : 1;           // the interior's first z-plane in the halo
+    static constexpr int VPT = N / T_;                 // interior voxels per thread
+    static constexpr int DZ = HY * HX, DY = HX;
+    static constexpr int NDIR = FLAT_ ? 4 : 6, DIR0 = FLAT_ ? 2 : 0;
+    static_assert(N % T_ == 0, "whole voxels per thread");
+    static_assert(T_ % 64 == 0 && T_ >= 64, "whole waves per tile");
+    static_assert(!FLAT_ || Z_ == 1, "a flat tile is one slice");
+    __device__ static __forceinline__ int halo_index(int vz, int vy, int vx) {
+        return ((vz + OZ) * HY + vy + 1) * HX + vx + 1;
+    }
+};
+using WsCube = WsShape<CC_WS_TZ, CC_WS_TY, CC_WS_TX, CC_WS_TT, false>;
+using WsFlat = WsShape<1, CC_WS_FY, CC_WS_FX, CC_WS_FT, true>;
 
 struct WsGeom {
     int64_t S[3], B[3];           // volume and block shape
@@ -103,28 +135,31 @@ __device__ __forceinline__ WsTile ws_tile(const WsGeom& g, int64_t t) {
 }
 
 // the tile's state with its halo into LDS (WS_INF outside the block)
+template <class G>
 __device__ __forceinline__ void ws_load_halo(const WsGeom& g, const WsTile& w, const u32* __restrict__ src, u32* H) {
     const int64_t YX = g.S[1] * g.S[2];
-    for (int i = threadIdx.x; i < WS_HN; i += WS_T) {
-        const int hz = i / (WS_HY * WS_HX), hy = (i / WS_HX) % WS_HY, hx = i % WS_HX;
-        const int64_t z = w.z0 - 1 + hz, y = w.y0 - 1 + hy, x = w.x0 - 1 + hx;
-        const bool inside_tile = hz >= 1 && hy >= 1 && hx >= 1 && hz <= w.lz && hy <= w.ly && hx <= w.lx;
+    for (int i = threadIdx.x; i < G::HN; i += G::T) {
+        const int hz = i / (G::HY * G::HX), hy = (i / G::HX) % G::HY, hx = i % G::HX;
+        const int64_t z = w.z0 - G::OZ + hz, y = w.y0 - 1 + hy, x = w.x0 - 1 + hx;
+        const bool inside_tile = hz >= G::OZ && hy >= 1 && hx >= 1 && hz < w.lz + G::OZ && hy <= w.ly && hx <= w.lx;
         const bool halo = !inside_tile && z >= w.e0[0] && z < w.e1[0] && y >= w.e0[1] && y < w.e1[1] &&
                           x >= w.e0[2] && x < w.e1[2];
         H[i] = (inside_tile || halo) ? src[z * YX + y * g.S[2] + x] : WS_INF;
     }
 }
 
-// the six neighbour tiles of the same block see a new halo: each goes on the next round's list
-// once (stamp = the round that listed it)
+// the face neighbour tiles of the same block (six, four of a flat tile) see a new halo: each goes
+// on the next round's list once (stamp = the round that listed it)
+template <class G>
 __device__ __forceinline__ void ws_list_neighbours(const WsGeom& g, const WsTile& w, int64_t t, u32* stamp, u32 round,
                                                    u32* list_out, u32* n_out) {
+    static_assert(G::T >= 6, "one thread per face neighbour");
     const int tid = threadIdx.x;
-    if (tid >= 6) return;
+    if (tid >= G::NDIR) return;
     const int64_t n2 = g.nt[2], zs = (int64_t)g.nt[1] * n2;
     bool ok = false;
     int64_t u = 0;
-    switch (tid) {
+    switch (tid + G::DIR0) {
         case 0: ok = w.iz > 0 && g.tblk[0][w.iz - 1] == w.bz; u = t - zs; break;
         case 1: ok = w.iz + 1 < g.nt[0] && g.tblk[0][w.iz + 1] == w.bz; u = t + zs; break;
         case 2: ok = w.iy > 0 && g.tblk[1][w.iy - 1] == w.by; u = t - n2; break;
@@ -135,28 +170,29 @@ __device__ __forceinline__ void ws_list_neighbours(const WsGeom& g, const WsTile
     if (ok && atomicExch(&stamp[u], round) != round) list_out[atomicAdd(n_out, 1u)] = (u32)u;
 }
 
-constexpr int WS_DZ = WS_HY * WS_HX, WS_DY = WS_HX;
-
 // label sweeps over the predecessor masks (bit d: the neighbour in direction d, in the order
 // -z, +z, -y, +y, -x, +x, is an optimal predecessor) to the tile's fixpoint; true if any changed
+template <class G>
 __device__ __forceinline__ bool ws_label_sweeps(const WsTile& w, u32* L, const u8* PM) {
     const int tid = threadIdx.x;
     bool tile_changed = false;
     for (int sweep = 0;; ++sweep) {
         bool chg = false;
 #pragma unroll
-        for (int k = 0; k < WS_VPT; ++k) {
-            const int j = tid + (CC_WS_ALT && (sweep & 1) ? WS_VPT - 1 - k : k) * WS_T;
+        for (int k = 0; k < G::VPT; ++k) {
+            const int j = tid + (CC_WS_ALT && (sweep & 1) ? G::VPT - 1 - k : k) * G::T;
             const u32 pm = PM[j];
             if (!pm) continue;
-            const int vz = j / (WS_Y * WS_X), vy = (j / WS_X) % WS_Y, vx = j % WS_X;
-            const int h = ((vz + 1) * WS_HY + vy + 1) * WS_HX + vx + 1;
+            const int vz = j / (G::Y * G::X), vy = (j / G::X) % G::Y, vx = j % G::X;
+            const int h = G::halo_index(vz, vy, vx);
             u32 l = L[h];
             const u32 l0 = l;
-            if (pm & 1u) l = min(l, L[h - WS_DZ]);
-            if (pm & 2u) l = min(l, L[h + WS_DZ]);
-            if (pm & 4u) l = min(l, L[h - WS_DY]);
-            if (pm & 8u) l = min(l, L[h + WS_DY]);
+            if (!G::FLAT) {
+                if (pm & 1u) l = min(l, L[h - G::DZ]);
+                if (pm & 2u) l = min(l, L[h + G::DZ]);
+            }
+            if (pm & 4u) l = min(l, L[h - G::DY]);
+            if (pm & 8u) l = min(l, L[h + G::DY]);
             if (pm & 16u) l = min(l, L[h - 1]);
             if (pm & 32u) l = min(l, L[h + 1]);
             if (l < l0) { L[h] = l; chg = true; }
@@ -167,26 +203,26 @@ __device__ __forceinline__ bool ws_label_sweeps(const WsTile& w, u32* L, const u
     return tile_changed;
 }
 
+template <class G>
 __device__ __forceinline__ void ws_store(const WsGeom& g, const WsTile& w, const u32* H, u32* dst) {
     const int64_t YX = g.S[1] * g.S[2];
-    for (int j = threadIdx.x; j < WS_Z * WS_Y * WS_X; j += WS_T) {
-        const int vz = j / (WS_Y * WS_X), vy = (j / WS_X) % WS_Y, vx = j % WS_X;
+    for (int j = threadIdx.x; j < G::N; j += G::T) {
+        const int vz = j / (G::Y * G::X), vy = (j / G::X) % G::Y, vx = j % G::X;
         if (vz >= w.lz || vy >= w.ly || vx >= w.lx) continue;
-        const int h = ((vz + 1) * WS_HY + vy + 1) * WS_HX + vx + 1;
-        dst[(int64_t)(w.z0 + vz) * YX + (int64_t)(w.y0 + vy) * g.S[2] + (w.x0 + vx)] = H[h];
+        dst[(int64_t)(w.z0 + vz) * YX + (int64_t)(w.y0 + vy) * g.S[2] + (w.x0 + vx)] = H[G::halo_index(vz, vy, vx)];
     }
 }
 
 // PHASE 1: one round of the costs over the round's tiles.  PHASE 2: every tile once on the
 // converged costs: each voxel's predecessor mask (pm), which is all the label rounds (k_ws_label)
 // read besides the labels (half their LDS, twice the resident tiles).
-template <int PHASE>
-__global__ __launch_bounds__(WS_T) void k_ws_relax(WsGeom g, const float* __restrict__ in, const u8* __restrict__ mask,
+template <int PHASE, class G>
+__global__ __launch_bounds__(G::T) void k_ws_relax(WsGeom g, const float* __restrict__ in, const u8* __restrict__ mask,
                                                    const u32* __restrict__ smin, const u32* __restrict__ smax,
                                                    const u32* __restrict__ sflag, u32* cost, u32* lab, u8* pm,
                                                    const u32* __restrict__ list_in, u32* stamp, u32 round,
                                                    u32* list_out, u32* n_out) {
-    __shared__ u32 C[WS_HN], F[WS_Z * WS_Y * WS_X];
+    __shared__ u32 C[G::HN], F[G::N];
     // the round's tiles: all (list_in NULL, the first round of a phase) or the listed ones
     const int64_t t = list_in ? (int64_t)list_in[blockIdx.x] : (int64_t)blockIdx.x;
     const int tid = threadIdx.x;
@@ -197,9 +233,9 @@ __global__ __launch_bounds__(WS_T) void k_ws_relax(WsGeom g, const float* __rest
     const float mn = __uint_as_float(ord2f(omn)), mxv = __uint_as_float(ord2f(omx));
     const float m = (isinf(mn) || isinf(mxv)) ? (isinf(mn) ? __uint_as_float(0x7FC00000u) : mxv - mn) : mxv - mn;
     const int64_t YX = g.S[1] * g.S[2];
-    ws_load_halo(g, w, cost, C);
-    for (int j = tid; j < WS_Z * WS_Y * WS_X; j += WS_T) {
-        const int vz = j / (WS_Y * WS_X), vy = (j / WS_X) % WS_Y, vx = j % WS_X;
+    ws_load_halo<G>(g, w, cost, C);
+    for (int j = tid; j < G::N; j += G::T) {
+        const int vz = j / (G::Y * G::X), vy = (j / G::X) % G::Y, vx = j % G::X;
         u32 f = WS_INF;
         if (vz < w.lz && vy < w.ly && vx < w.lx) {
             const int64_t o = (int64_t)(w.z0 + vz) * YX + (int64_t)(w.y0 + vy) * g.S[2] + (w.x0 + vx);
@@ -210,70 +246,71 @@ __global__ __launch_bounds__(WS_T) void k_ws_relax(WsGeom g, const float* __rest
     __syncthreads();
     bool tile_changed = false;
     if (PHASE == 1) {
-        // voxel-by-voxel (Gauss-Seidel) sweeps: each voxel against its six neighbours
+        // voxel-by-voxel (Gauss-Seidel) sweeps: each voxel against its face neighbours
         for (int sweep = 0;; ++sweep) {
             bool chg = false;
 #pragma unroll
-            for (int k = 0; k < WS_VPT; ++k) {
-                const int j = tid + (CC_WS_ALT && (sweep & 1) ? WS_VPT - 1 - k : k) * WS_T;
-                const int vz = j / (WS_Y * WS_X), vy = (j / WS_X) % WS_Y, vx = j % WS_X;
+            for (int k = 0; k < G::VPT; ++k) {
+                const int j = tid + (CC_WS_ALT && (sweep & 1) ? G::VPT - 1 - k : k) * G::T;
+                const int vz = j / (G::Y * G::X), vy = (j / G::X) % G::Y, vx = j % G::X;
                 if (vz >= w.lz || vy >= w.ly || vx >= w.lx) continue;
-                const int h = ((vz + 1) * WS_HY + vy + 1) * WS_HX + vx + 1;
+                const int h = G::halo_index(vz, vy, vx);
                 const u32 c = C[h];
                 if (c == 0u) continue;                               // a seed
-                const u32 best = min(min(min(C[h - WS_DZ], C[h + WS_DZ]), min(C[h - WS_DY], C[h + WS_DY])),
-                                     min(C[h - 1], C[h + 1]));
+                u32 best = min(min(C[h - G::DY], C[h + G::DY]), min(C[h - 1], C[h + 1]));
+                if (!G::FLAT) best = min(min(C[h - G::DZ], C[h + G::DZ]), best);
                 const u32 cand = best == WS_INF ? WS_INF : max(best, F[j]);
                 if (cand < c) { C[h] = cand; chg = true; }
             }
             if (!__syncthreads_or(chg)) break;
             tile_changed = true;
         }
-        if (tile_changed) ws_store(g, w, C, cost);
+        if (tile_changed) ws_store<G>(g, w, C, cost);
     } else {
-        for (int j = tid; j < WS_Z * WS_Y * WS_X; j += WS_T) {
-            const int vz = j / (WS_Y * WS_X), vy = (j / WS_X) % WS_Y, vx = j % WS_X;
+        for (int j = tid; j < G::N; j += G::T) {
+            const int vz = j / (G::Y * G::X), vy = (j / G::X) % G::Y, vx = j % G::X;
             if (vz >= w.lz || vy >= w.ly || vx >= w.lx) continue;
-            const int h = ((vz + 1) * WS_HY + vy + 1) * WS_HX + vx + 1;
+            const int h = G::halo_index(vz, vy, vx);
             const u32 c = C[h], f = F[j];
             u32 bits = 0;
             if (c != 0u && c != WS_INF) {
-                const int off[6] = {-WS_DZ, WS_DZ, -WS_DY, WS_DY, -1, 1};
+                const int off[6] = {-G::DZ, G::DZ, -G::DY, G::DY, -1, 1};
 #pragma unroll
-                for (int d = 0; d < 6; ++d) {
+                for (int d = G::DIR0; d < 6; ++d) {
                     const u32 cu = C[h + off[d]];
                     if (cu != WS_INF && max(cu, f) == c) bits |= 1u << d;
                 }
             }
-                pm[(int64_t)(w.z0 + vz) * YX + (int64_t)(w.y0 + vy) * g.S[2] + (w.x0 + vx)] = (u8)bits;
+            pm[(int64_t)(w.z0 + vz) * YX + (int64_t)(w.y0 + vy) * g.S[2] + (w.x0 + vx)] = (u8)bits;
         }
         return;                                       // the label rounds are k_ws_label's
     }
-    if (tile_changed) ws_list_neighbours(g, w, t, stamp, round, list_out, n_out);
+    if (tile_changed) ws_list_neighbours<G>(g, w, t, stamp, round, list_out, n_out);
 }
 
 // a label round over the listed tiles (list_in NULL: every tile): labels with halo and the
 // predecessor masks
-__global__ __launch_bounds__(WS_T) void k_ws_label(WsGeom g, const u8* __restrict__ pm, u32* lab,
+template <class G>
+__global__ __launch_bounds__(G::T) void k_ws_label(WsGeom g, const u8* __restrict__ pm, u32* lab,
                                                    const u32* __restrict__ list_in, u32* stamp, u32 round,
                                                    u32* list_out, u32* n_out) {
-    __shared__ u32 Lsh[WS_HN];
-    __shared__ u8 PM[WS_Z * WS_Y * WS_X];
+    __shared__ u32 Lsh[G::HN];
+    __shared__ u8 PM[G::N];
     const int64_t t = list_in ? (int64_t)list_in[blockIdx.x] : (int64_t)blockIdx.x;
     const WsTile w = ws_tile(g, t);
     const int64_t YX = g.S[1] * g.S[2];
-    ws_load_halo(g, w, lab, Lsh);
-    for (int j = threadIdx.x; j < WS_Z * WS_Y * WS_X; j += WS_T) {
-        const int vz = j / (WS_Y * WS_X), vy = (j / WS_X) % WS_Y, vx = j % WS_X;
+    ws_load_halo<G>(g, w, lab, Lsh);
+    for (int j = threadIdx.x; j < G::N; j += G::T) {
+        const int vz = j / (G::Y * G::X), vy = (j / G::X) % G::Y, vx = j % G::X;
         u8 bits = 0;
         if (vz < w.lz && vy < w.ly && vx < w.lx)
             bits = pm[(int64_t)(w.z0 + vz) * YX + (int64_t)(w.y0 + vy) * g.S[2] + (w.x0 + vx)];
         PM[j] = bits;
     }
     __syncthreads();
-    if (ws_label_sweeps(w, Lsh, PM)) {
-        ws_store(g, w, Lsh, lab);
-        ws_list_neighbours(g, w, t, stamp, round, list_out, n_out);
+    if (ws_label_sweeps<G>(w, Lsh, PM)) {
+        ws_store<G>(g, w, Lsh, lab);
+        ws_list_neighbours<G>(g, w, t, stamp, round, list_out, n_out);
     }
 }
 
@@ -410,6 +447,135 @@ extern "C" int cc_normalize_channels(cc_ctx* c, const float* in, int64_t n_chann
     })
 }
 
+namespace cc {
+
+// the watershed tiles of geometry G: per axis, tiles of G's extent from each block's origin; the
+// tables go to c->ws_tab.  Returns the number of tiles.
+template <class G>
+static int64_t ws_tiles(cc_ctx* c, const int64_t shape[3], const int64_t block_shape[3], WsGeom& g) {
+    hipStream_t s = cstream(c);
+    std::memset(&g, 0, sizeof(g));
+    const int T[3] = {G::Z, G::Y, G::X};
+    std::vector<int32_t>& tab = c->h_ws;          // alive until the stream has copied it
+    tab.clear();
+    std::vector<int32_t> st3[3], ln3[3], bk3[3];
+    for (int a = 0; a < 3; ++a) {
+        g.S[a] = shape[a];
+        g.B[a] = block_shape[a];
+        g.nb[a] = (int32_t)((shape[a] + block_shape[a] - 1) / block_shape[a]);
+        for (int64_t bb = 0; bb < g.nb[a]; ++bb) {
+            const int64_t b0 = bb * block_shape[a], b1 = std::min(b0 + block_shape[a], shape[a]);
+            for (int64_t p = b0; p < b1; p += T[a]) {
+                st3[a].push_back((int32_t)p);
+                ln3[a].push_back((int32_t)std::min<int64_t>(T[a], b1 - p));
+                bk3[a].push_back((int32_t)bb);
+            }
+        }
+        g.nt[a] = (int32_t)st3[a].size();
+    }
+    for (int a = 0; a < 3; ++a) {
+        tab.insert(tab.end(), st3[a].begin(), st3[a].end());
+        tab.insert(tab.end(), ln3[a].begin(), ln3[a].end());
+        tab.insert(tab.end(), bk3[a].begin(), bk3[a].end());
+    }
+    const int64_t nt = (int64_t)g.nt[0] * g.nt[1] * g.nt[2];
+    CC_REQUIRE(nt < (1LL << 31), "too many watershed tiles");
+    c->ws_tab.ensure(tab.size() * sizeof(int32_t));
+    HIP_OK(hipMemcpyAsync(c->ws_tab.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    const int32_t* p = c->ws_tab.as<int32_t>();
+    for (int a = 0; a < 3; ++a) {
+        g.tstart[a] = p; p += g.nt[a];
+        g.tlen[a] = p; p += g.nt[a];
+        g.tblk[a] = p; p += g.nt[a];
+    }
+    return nt;
+}
+
+// state: cost | label per voxel; per tile the round that last listed it, two tile lists; the
+// predecessor masks; flags: [0] seed id error, [1] tiles listed for the next round
+struct WsState {
+    u32 *cost, *lab, *stamp, *list0, *list1, *flags;
+    u8* pm;
+    u32 round;
+};
+
+static WsState ws_state(cc_ctx* c, int64_t n, int64_t nt) {
+    hipStream_t s = cstream(c);
+    WsState w;
+    c->ws_buf.ensure((size_t)n * 2 * sizeof(u32) + 3 * (size_t)nt * sizeof(u32) + (size_t)n + 64);
+    w.cost = c->ws_buf.as<u32>();
+    w.lab = w.cost + n;
+    w.stamp = w.lab + n;
+    w.list0 = w.stamp + nt;
+    w.list1 = w.list0 + nt;
+    w.pm = (u8*)(w.list1 + nt);                   // predecessor masks (the first label round)
+    c->counter.ensure(4 * sizeof(u32));
+    w.flags = c->counter.as<u32>();
+    w.round = 0;
+    HIP_OK(hipMemsetAsync(w.flags, 0, 4 * sizeof(u32), s));
+    HIP_OK(hipMemsetAsync(w.stamp, 0, nt * sizeof(u32), s));
+    return w;
+}
+
+// both phases on the initialised costs and labels of `w`: rounds of launches until no tile
+// changes.  Returns the rounds run.  w.round goes on counting, so a second pass over the same
+// stamps lists correctly.
+template <class G>
+static int64_t ws_rounds(cc_ctx* c, const WsGeom& g, int64_t nt, int64_t n, const float* in, const u8* mask,
+                         const u32* smin, const u32* smax, const u32* sflag, WsState& w) {
+    hipStream_t s = cstream(c);
+    int64_t total_rounds = 0;
+    const bool trace = std::getenv("CC_WS_TRACE") != nullptr;
+    auto tr0 = std::chrono::steady_clock::now();
+    const char* const names[3] = {G::FLAT ? "k_ws2_preds" : "k_ws_preds", G::FLAT ? "k_ws2_relax_cost" : "k_ws_relax_cost",
+                                  G::FLAT ? "k_ws2_relax_label" : "k_ws_relax_label"};
+    for (int phase = 1; phase <= 2; ++phase) {
+        // the first round of a phase visits every tile, later rounds the tiles listed by the last
+        const u32* lin = nullptr;
+        int64_t ntile = nt;
+        if (phase == 2)
+            launch(c, names[0], [&] {
+                k_ws_relax<2, G><<<(unsigned)nt, G::T, 0, s>>>(g, in, mask, smin, smax, sflag, w.cost, w.lab, w.pm, nullptr,
+                                                              w.stamp, w.round, w.list1, w.flags + 1);
+            });
+        for (int64_t r = 0; ntile > 0; ++r) {
+            CC_REQUIRE(r < 4 * n + 16, "watershed did not converge");
+            ++w.round;
+            HIP_OK(hipMemsetAsync(w.flags + 1, 0, sizeof(u32), s));
+            launch(c, names[phase], [&] {
+                if (phase == 1)
+                    k_ws_relax<1, G><<<(unsigned)ntile, G::T, 0, s>>>(g, in, mask, smin, smax, sflag, w.cost, w.lab, w.pm,
+                                                                     lin, w.stamp, w.round, w.list1, w.flags + 1);
+                else
+                    k_ws_label<G><<<(unsigned)ntile, G::T, 0, s>>>(g, w.pm, w.lab, lin, w.stamp, w.round, w.list1,
+                                                                  w.flags + 1);
+            });
+            u32 fl[2] = {0, 0};
+            {
+                Readback rb(c, 64);
+                rb.add(fl, w.flags, 2 * sizeof(u32));
+                rb.wait();
+            }
+            CC_REQUIRE(!(fl[0] & 1u), "seed ids must be < 2^32 - 1 (the reference casts seeds to uint32)");
+            CC_REQUIRE(!(fl[0] & 2u), "watershed_domains: a seed id above its domain's count");
+            ++total_rounds;
+            CC_REQUIRE(fl[1] <= (u32)nt, "watershed tile list overflow");
+            std::swap(w.list0, w.list1);
+            lin = w.list0;
+            if (trace) {                          // dev hook: tiles and host ms per round
+                const auto now = std::chrono::steady_clock::now();
+                std::fprintf(stderr, "ws phase %d round %ld tiles %ld ms %.3f\n", phase, (long)r, (long)ntile,
+                             std::chrono::duration<double, std::milli>(now - tr0).count());
+                tr0 = now;
+            }
+            ntile = fl[1];
+        }
+    }
+    return total_rounds;
+}
+
+}  // namespace cc
+
 extern "C" int cc_watershed_from_seeds(cc_ctx* c, const float* in, const uint64_t* seeds, const uint8_t* mask,
                                        const int64_t shape[3], const int64_t block_shape[3], uint64_t* out,
                                        int64_t* rounds) {
@@ -443,100 +609,12 @@ extern "C" int cc_watershed_from_seeds(cc_ctx* c, const float* in, const uint64_
             HIP_OK(hipMemsetAsync(smax, 0x00, 2 * nb * sizeof(u32), s));
             launch(c, "k_block_stats", [&] { k_block_stats<<<(unsigned)gg.n_tiles, NTHREADS, 0, s>>>(gg, in, smin, smax, sflag); });
         }
-        // the watershed tiles: per axis, tiles of WS_* from each block's origin
         WsGeom g;
-        std::memset(&g, 0, sizeof(g));
-        const int T[3] = {WS_Z, WS_Y, WS_X};
-        std::vector<int32_t> tab;
-        std::vector<int32_t> st3[3], ln3[3], bk3[3];
-        for (int a = 0; a < 3; ++a) {
-            g.S[a] = shape[a];
-            g.B[a] = block_shape[a];
-            g.nb[a] = (int32_t)((shape[a] + block_shape[a] - 1) / block_shape[a]);
-            for (int64_t bb = 0; bb < g.nb[a]; ++bb) {
-                const int64_t b0 = bb * block_shape[a], b1 = std::min(b0 + block_shape[a], shape[a]);
-                for (int64_t p = b0; p < b1; p += T[a]) {
-                    st3[a].push_back((int32_t)p);
-                    ln3[a].push_back((int32_t)std::min<int64_t>(T[a], b1 - p));
-                    bk3[a].push_back((int32_t)bb);
-                }
-            }
-            g.nt[a] = (int32_t)st3[a].size();
-        }
-        for (int a = 0; a < 3; ++a) {
-            tab.insert(tab.end(), st3[a].begin(), st3[a].end());
-            tab.insert(tab.end(), ln3[a].begin(), ln3[a].end());
-            tab.insert(tab.end(), bk3[a].begin(), bk3[a].end());
-        }
-        const int64_t nt = (int64_t)g.nt[0] * g.nt[1] * g.nt[2];
-        CC_REQUIRE(nt < (1LL << 31), "too many watershed tiles");
-        c->ws_tab.ensure(tab.size() * sizeof(int32_t));
-        HIP_OK(hipMemcpyAsync(c->ws_tab.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        {
-            const int32_t* p = c->ws_tab.as<int32_t>();
-            for (int a = 0; a < 3; ++a) {
-                g.tstart[a] = p; p += g.nt[a];
-                g.tlen[a] = p; p += g.nt[a];
-                g.tblk[a] = p; p += g.nt[a];
-            }
-        }
-        // state: cost | label per voxel; per tile the round that last listed it, two tile lists
-        c->ws_buf.ensure((size_t)n * 2 * sizeof(u32) + 3 * (size_t)nt * sizeof(u32) + (size_t)n + 64);
-        u32* cost = c->ws_buf.as<u32>();
-        u32* lab = cost + n;
-        u32* stamp = lab + n;
-        u32* list0 = stamp + nt;
-        u32* list1 = list0 + nt;
-        u8* pm = (u8*)(list1 + nt);                   // predecessor masks (the first label round)
-        c->counter.ensure(4 * sizeof(u32));
-        u32* flags = c->counter.as<u32>();            // [0] seed id overflow, [1] tiles listed for the next round
-        HIP_OK(hipMemsetAsync(flags, 0, 4 * sizeof(u32), s));
-        HIP_OK(hipMemsetAsync(stamp, 0, nt * sizeof(u32), s));
-        launch(c, "k_ws_init", [&] { k_ws_init<<<grid_stride(n), 256, 0, s>>>(n, seeds, cost, lab, flags); });
-        int64_t total_rounds = 0;
-        u32 round = 0;
-        const bool trace = std::getenv("CC_WS_TRACE") != nullptr;
-        auto tr0 = std::chrono::steady_clock::now();
-        for (int phase = 1; phase <= 2; ++phase) {
-            // the first round of a phase visits every tile, later rounds the tiles listed by the last
-            const u32* lin = nullptr;
-            int64_t ntile = nt;
-            if (phase == 2)
-                launch(c, "k_ws_preds", [&] {
-                    k_ws_relax<2><<<(unsigned)nt, WS_T, 0, s>>>(g, in, mask, smin, smax, sflag, cost, lab, pm, nullptr,
-                                                               stamp, round, list1, flags + 1);
-                });
-            for (int64_t r = 0; ntile > 0; ++r) {
-                CC_REQUIRE(r < 4 * n + 16, "watershed did not converge");
-                ++round;
-                HIP_OK(hipMemsetAsync(flags + 1, 0, sizeof(u32), s));
-                launch(c, phase == 1 ? "k_ws_relax_cost" : "k_ws_relax_label", [&] {
-                    if (phase == 1)
-                        k_ws_relax<1><<<(unsigned)ntile, WS_T, 0, s>>>(g, in, mask, smin, smax, sflag, cost, lab, pm, lin,
-                                                                      stamp, round, list1, flags + 1);
-                    else
-                        k_ws_label<<<(unsigned)ntile, WS_T, 0, s>>>(g, pm, lab, lin, stamp, round, list1, flags + 1);
-                });
-                u32 fl[2] = {0, 0};
-                {
-                    Readback rb(c, 64);
-                    rb.add(fl, flags, 2 * sizeof(u32));
-                    rb.wait();
-                }
-                CC_REQUIRE(!(fl[0] & 1u), "seed ids must be < 2^32 - 1 (the reference casts seeds to uint32)");
-                ++total_rounds;
-                CC_REQUIRE(fl[1] <= (u32)nt, "watershed tile list overflow");
-                std::swap(list0, list1);
-                lin = list0;
-                if (trace) {                          // dev hook: tiles and host ms per round
-                    const auto now = std::chrono::steady_clock::now();
-                    std::fprintf(stderr, "ws phase %d round %ld tiles %ld ms %.3f\n", phase, (long)r, (long)ntile,
-                                 std::chrono::duration<double, std::milli>(now - tr0).count());
-                    tr0 = now;
-                }
-                ntile = fl[1];
-            }
-        }
+        const int64_t nt = ws_tiles<WsCube>(c, shape, block_shape, g);
+        WsState w = ws_state(c, n, nt);
+        launch(c, "k_ws_init", [&] { k_ws_init<<<grid_stride(n), 256, 0, s>>>(n, seeds, w.cost, w.lab, w.flags); });
+        const int64_t total_rounds = ws_rounds<WsCube>(c, g, nt, n, in, mask, smin, smax, sflag, w);
+        u32* lab = w.lab;
         launch(c, "k_ws_write", [&] { k_ws_write<<<grid_stride(n), 256, 0, s>>>(n, lab, mask, out); });
         sync(c);
         if (rounds) *rounds = total_rounds;

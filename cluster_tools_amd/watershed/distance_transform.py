@@ -58,11 +58,8 @@ def device_objects(ctx, xd, block_shape, config, mask=None):
     if xd.dim() == 3 and not invert:
         obj = ctx.threshold(xd, block_shape, thr, 'greater')
     else:
-        # the normalized values themselves: of one channel, its maximum over the channels
-        xn = (ctx.normalize_channels(xd, block_shape, config.get('agglomerate_channels', 'mean')) if xd.dim() == 4
-              else ctx.normalize_channels(xd[None], block_shape, 'max'))
-        if invert:
-            xn = 1. - xn
+        # the normalized values themselves
+        xn = ctx.normalized_input(xd, block_shape, config.get('agglomerate_channels', 'mean'), invert)
         # a float32 compare, as numpy's of a float32 array with a python float
         obj = (xn > torch.tensor(float(np.float32(thr)), dtype=torch.float32, device=xn.device)).to(torch.uint8)
     if mask is not None:

@@ -643,6 +643,60 @@ int cc_local_maxima_seeds(cc_ctx* ctx, const float* values_dev, const int64_t sh
                           const int64_t domain_shape[3], int indirect, uint64_t* seeds_dev,
                           uint64_t* counts_dev /* nullable */);
 
+/* --- The distance-transform watershed: height map, watershed per domain, size filter -----
+ * The last stages of the reference's distance-transform watershed (watershed/watershed.py:
+ * _make_hmap :164-170, _apply_watershed :212-250).  In both entries a domain is a whole block of
+ * the reference blocking (apply_2d = 0) or each z-slice of each block (apply_2d != 0), domains are
+ * independent, and the domain index is the raster order of the domain grid, z slowest, as in
+ * cc_local_maxima_seeds with domain_shape = block_shape or (1, by, bx).
+ *
+ * Height map.  in_dev is the task's input at that point (normalized per block, inverted if asked,
+ * 1 outside the mask), dt_dev the distance transform (cc_distance_transform; finite, a NaN in it is
+ * unpinned); both shape[0] x shape[1] x shape[2] float32.  Per domain, all in float32 and every
+ * operation rounded on its own (no FMA contraction):
+ *   n = vu.normalize(dt): dt - min, then / max of that if it is > 0 (a domain of constant dt, one
+ *       without an object voxel, gives n = 0);
+ *   h = fl(fl(a in) + fl(b fl(1 - n))), a = (float)alpha, b = (float)(1.0 - alpha) with the
+ *       subtraction in double: numpy's `alpha * input_ + (1. - alpha) * distances` of float32
+ *       arrays and Python floats.
+ * If sigma_weights != 0 the filter of cc_gaussian_smooth_domains follows (same apply_2d, same
+ * error rules: sigma > 0, every filtered block line longer than the kernel radius).  out_dev may be
+ * in_dev.  Every check of the arguments precedes the first device call; a shape with a zero
+ * dimension writes nothing. */
+int cc_watershed_height_map(cc_ctx* ctx, const float* in_dev, const float* dt_dev, const int64_t shape[3],
+                            const int64_t block_shape[3], int apply_2d, double alpha, double sigma_weights,
+                            float* out_dev);
+
+/* Watershed per domain.  The definition is cc_watershed_from_seeds', except that the values are
+ * taken as they are (f(v) = the ordered u32 of values[v], NaN -> 0xFFFFFFFE: no normalize, and the
+ * mask does not touch them -- the caller has put 1 into the input outside the mask) and that it
+ * runs per domain: a slice domain sees only its 4 in-slice neighbours.
+ *   seeds   what cc_local_maxima_seeds returns: ids 1 .. counts_dev[d] inside domain d, 0 elsewhere
+ *           (uint64; counts_dev one uint64 per domain, their sum at most the volume's voxels).  An
+ *           id above counts_dev[d] is an error, found by the first pass over the seeds.
+ *   filter  size_filter > 0 (run_watershed(..., size_filter), elf's apply_size_filter): after the
+ *           first watershed the size of label l of domain d is its voxel count in d, voxels
+ *           outside the mask included (the reference filters before it masks); every label of
+ *           size < size_filter becomes 0, and the watershed runs a second time over the same values
+ *           with the surviving regions as seeds.  A domain in which nothing survives stays all 0
+ *           with max_id 0; vigra would seed such a domain itself: this case is unpinned.
+ *   mask    (optional, uint8, same shape) the output is 0 where the mask is 0.
+ *   max_ids (optional, one uint64 per domain) the largest output label of d over the in-mask voxels
+ *           (the reference's max_id, :227 / :236) -- not the seed count.
+ *   rounds  (optional, TWO int64) the relaxation rounds of the first and of the second watershed
+ *           (0 without a filter).
+ * Slice domains run on flat tiles of 1 x 32 x 64 voxels with a halo in y and x only, block
+ * domains on cc_watershed_from_seeds' 8 x 8 x 32 tiles.  out_dev may be seeds_dev.  Limits: every
+ * dimension below 2^31, shape[0] * shape[1] below 2^31, fewer than 65536 domains along x, a domain
+ * holds fewer than 2^32 voxels.  A shape with a zero dimension writes nothing.  Every check that
+ * needs no device read (NULL arguments, a negative size_filter, the limits) precedes the first
+ * device call; invalid arguments return -1 with a message. */
+int cc_watershed_domains(cc_ctx* ctx, const float* values_dev, const uint64_t* seeds_dev,
+                         const uint64_t* counts_dev, const uint8_t* mask_dev /* nullable */,
+                         const int64_t shape[3], const int64_t block_shape[3], int apply_2d,
+                         int64_t size_filter, uint64_t* out_dev, uint64_t* max_ids_dev /* nullable, per domain */,
+                         int64_t* rounds /* nullable, 2 */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,15 @@ allow_retry, the parameters with their defaults and default_task_config().
 
 tests/test_task_framework.py rebuilds the same dict from the current classes and compares it with
 the committed dump, so regenerate the dump only where a task's surface is meant to change.
+
+The dump is split over files.  A module of tasks added later is listed in ADDENDA and dumped into a
+file of its own, which tests/test_task_surface_addenda.py compares in the same way:
+
+    python tools/dump_task_surface.py watershed > tests/golden/task_surface_watershed.json
+
+task_surface() covers every module that no addendum claims, so a new *Local task fails the first
+comparison until it is either dumped there or claimed by an addendum; every task is in exactly one
+file.
 """
 import importlib
 import inspect
@@ -30,9 +39,17 @@ def _default(param):
     return type(d).__name__            # a task instance (dependency = DummyTask())
 
 
-def task_surface():
+# addendum name -> the modules whose tasks tests/golden/task_surface_<name>.json holds
+ADDENDA = {'watershed': ('cluster_tools_amd.watershed.watershed',)}
+
+
+def task_surface(addendum=None):
+    """The surface of the tasks of the addendum's modules; None: of every module no addendum claims."""
+    claimed = {m for mods in ADDENDA.values() for m in mods}
     surface = {}
     for info in pkgutil.walk_packages(cluster_tools_amd.__path__, 'cluster_tools_amd.'):
+        if (info.name in claimed) if addendum is None else (info.name not in ADDENDA[addendum]):
+            continue
         module = importlib.import_module(info.name)
         for name, klass in inspect.getmembers(module, inspect.isclass):
             if not (name.endswith('Local') and issubclass(klass, BaseClusterTask)
@@ -49,5 +66,5 @@ def task_surface():
 
 
 if __name__ == '__main__':
-    json.dump(task_surface(), sys.stdout, indent=1, sort_keys=True)
+    json.dump(task_surface(sys.argv[1] if len(sys.argv) > 1 else None), sys.stdout, indent=1, sort_keys=True)
     sys.stdout.write('\n')
