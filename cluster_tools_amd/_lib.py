@@ -33,7 +33,7 @@ EXPORTS = (
     'cc_label_sizes', 'cc_size_filter', 'cc_morphology', 'cc_region_features',
     'cc_region_graph', 'cc_edge_features', 'cc_label_overlaps', 'cc_max_overlaps', 'cc_affinity_features',
     'cc_distance_transform', 'cc_gaussian_smooth_domains', 'cc_local_maxima_seeds',
-    'cc_watershed_height_map', 'cc_watershed_domains',
+    'cc_watershed_height_map', 'cc_watershed_domains', 'cc_multicut_gaec', 'cc_multicut_live_edges',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -179,6 +179,8 @@ def load(host_only=False):
         'cc_local_maxima_seeds': (I, [P, P, P, P, I, P, P]),
         'cc_watershed_height_map': (I, [P, P, P, P, P, I, ctypes.c_double, ctypes.c_double, P]),
         'cc_watershed_domains': (I, [P, P, P, P, P, P, P, I, ctypes.c_int64, P, P, P]),
+        'cc_multicut_gaec': (I, [P, P, P, I, i64, i64, P, P, P]),
+        'cc_multicut_live_edges': (i64, [P, P, i64]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -318,6 +320,21 @@ def _ignore_in(table, ignore_label):
     k = np.searchsorted(table[:, 0], np.uint64(ignore_label))
     present = k < len(table) and table[k, 0] == np.uint64(ignore_label)
     return int(table[k, 1]) if present else int(table[-1, 1]) + 1
+
+
+def multicut_energy(edges, costs, labels):
+    """The multicut energy of a node labelling on the host (numpy): the sum of the costs of the
+    rows (u, v) of `edges` with labels[u] != labels[v], as the balanced binary tree over the rows
+    that cc_multicut_gaec evaluates (include/cc_mi355x.h), so the two agree to the bit."""
+    edges = np.asarray(edges).reshape(-1, 2).astype(np.int64)
+    labels = np.asarray(labels)
+    if len(edges) == 0:
+        return 0.0
+    x = np.where(labels[edges[:, 0]] != labels[edges[:, 1]], np.asarray(costs).astype(np.float64), 0.0)
+    x = np.concatenate([x, np.zeros((1 << int(len(x) - 1).bit_length()) - len(x))])
+    while len(x) > 1:
+        x = x[0::2] + x[1::2]
+    return float(x[0])
 
 
 def mode_id(mode):
@@ -1133,6 +1150,36 @@ class Context:
         labels, max_ids = self.watershed_domains(hmap, seeds, counts, block_shape, mask, apply_2d=ws_2d,
                                                  size_filter=config.get('size_filter', 25), out=seeds)
         return (labels, max_ids, obj) if return_objects else (labels, max_ids)
+
+    def multicut(self, edges, costs, n_nodes=None, return_stats=False):
+        """Multicut of a weighted graph on device by parallel greedy additive edge contraction
+        (cc_multicut_gaec; the definition is in include/cc_mi355x.h).  edges: (n, 2) CUDA tensor of
+        8-byte node ids; costs: (n,) float32 or float64 CUDA tensor, > 0 attractive; n_nodes None:
+        edges.max() + 1.  Returns the node labels (n_nodes,) as torch int64 -- a node's label is the
+        smallest node id of its cluster -- and with return_stats a dict of the rounds run, the
+        multicut energy and the live edges of the contracted graph before each round and after the
+        last."""
+        import torch
+        assert hasattr(edges, 'data_ptr') and edges.is_cuda and edges.element_size() == 8 and edges.is_contiguous()
+        assert edges.dim() == 2 and edges.shape[1] == 2
+        assert costs.is_cuda and costs.dtype in (torch.float32, torch.float64) and costs.is_contiguous()
+        assert costs.shape == (edges.shape[0],)
+        n = int(edges.shape[0])
+        if n_nodes is None:
+            n_nodes = int(edges.view(torch.int64).max()) + 1 if n else 0
+        n_nodes = int(n_nodes)
+        # the ctx runs on its own stream: the inputs may still be in flight on torch's
+        torch.cuda.current_stream(edges.device).synchronize()
+        labels = torch.empty(max(n_nodes, 0), dtype=torch.int64, device=edges.device)
+        rounds, energy = ctypes.c_int64(0), ctypes.c_double(0.)
+        _check(load().cc_multicut_gaec(self._h, _ptr(edges) if n else None, _ptr(costs) if n else None,
+                                       DTYPES[str(costs.dtype).split('.')[-1]], n, n_nodes,
+                                       _ptr(labels) if n_nodes > 0 else None, ctypes.byref(rounds), ctypes.byref(energy)))
+        if not return_stats:
+            return labels
+        live = np.zeros(rounds.value + 1, dtype=np.int64)
+        m = load().cc_multicut_live_edges(self._h, _ptr(live), len(live))
+        return labels, {'rounds': int(rounds.value), 'energy': float(energy.value), 'live_edges': live[:max(m, 0)].tolist()}
 
     def evaluate(self, seg, gt, block_shape, ignore_label=0):
         """EvaluationWorkflow (evaluation/evaluation_workflow.py:46-84) on device: overlaps per

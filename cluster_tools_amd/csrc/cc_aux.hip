@@ -5,7 +5,7 @@
 // (cc_edge_features.hip, from affinity maps cc_affinity_features.hip), the channel / Gaussian prefilter (cc_prefilter.hip) and the seeded
 // watershed (cc_watershed.hip), the distance transform (cc_distance_transform.hip), the watershed
 // seeds (cc_seeds.hip) and the distance-transform watershed's height map, size filter and domains
-// (cc_dt_watershed.hip), with their C-ABI entries.
+// (cc_dt_watershed.hip) and the multicut solver (cc_multicut.hip), with their C-ABI entries.
 //
 // A unit of its own because the HIP runtime loads a code object whole, every kernel of it, at
 // the first launch from it: kept apart, the ~60 kernels here (the prefilter's 40 template
@@ -43,3 +43,4 @@ __global__ __launch_bounds__(NTHREADS) void k_block_stats(Geom g, const float* _
 #include "cc_distance_transform.hip"
 #include "cc_seeds.hip"
 #include "cc_dt_watershed.hip"
+#include "cc_multicut.hip"

@@ -268,7 +268,8 @@ struct cc_ctx {
         ws_tab, ws_buf,                                   // seeded watershed (cc_watershed.hip)
         dt_a, dt_b,                                       // distance transform: pass intermediates (cc_distance_transform.hip)
         sd_flags, sd_rows,                                // watershed seeds: flag bytes, row-segment counts (cc_seeds.hip)
-        wd_stat, wd_off, wd_hist;                         // watershed domains: statistics, id offsets, label sizes (cc_dt_watershed.hip)
+        wd_stat, wd_off, wd_hist,                         // watershed domains: statistics, id offsets, label sizes (cc_dt_watershed.hip)
+        mc_nodes, mc_edges, mc_part;                      // multicut: per-node state, the two edge lists, energy partial sums (cc_multicut.hip)
     int64_t ev_cap = 0;      // entries per evaluation hash table of the last cc_evaluate
     int64_t rl_cap = 0;      // id-set slots of the last cc_relabel_consecutive
     int64_t sf_cap = 0;      // count-table slots of the last cc_label_sizes / cc_size_filter
@@ -277,6 +278,7 @@ struct cc_ctx {
     int64_t gr_cap = 0;      // table slots of the last cc_region_graph
     int64_t nl_cap = 0;      // table slots of the last cc_label_overlaps
     int64_t nl_n = -1;       // triples the last cc_label_overlaps left in nl_sorted (-1: none)
+    std::vector<int64_t> mc_live;   // live edges before round 0, 1, ... and after the last of the last cc_multicut_gaec
     // last run
     int64_t n_blocks = 0;
     uint64_t n_labels = 0;
@@ -318,7 +320,7 @@ static inline std::vector<DevBuf*> ctx_bufs(cc_ctx* c) {
             &c->ipairs, &c->ipc, &c->iovf, &c->spec, &c->mark, &c->bflag, &c->ev_main, &c->ev_z, &c->ev_seg, &c->ev_gt,
             &c->ev_flag, &c->ev_part, &c->rl_wg, &c->sf_tab, &c->sf_comp, &c->sf_sorted, &c->sf_list, &c->mo_tab, &c->mo_rows, &c->rf_tab, &c->rf_rows, &c->gr_tab, &c->gr_comp,
             &c->gr_sorted, &c->ef_tab, &c->nl_tab, &c->nl_flag, &c->nl_comp, &c->nl_sorted, &c->nl_max, &c->gs1, &c->gs2, &c->gs_tab, &c->mask_xmap, &c->mlive, &c->seam_hash, &c->ws_tab,
-            &c->ws_buf, &c->dt_a, &c->dt_b, &c->sd_flags, &c->sd_rows, &c->wd_stat, &c->wd_off, &c->wd_hist, &c->status, &c->hmap_keys, &c->hmap_par};
+            &c->ws_buf, &c->dt_a, &c->dt_b, &c->sd_flags, &c->sd_rows, &c->wd_stat, &c->wd_off, &c->wd_hist, &c->mc_nodes, &c->mc_edges, &c->mc_part, &c->status, &c->hmap_keys, &c->hmap_par};
 }
 
 // the context's stream: the caller's (cc_set_stream), else the null stream -- which is torch's

@@ -697,6 +697,50 @@ int cc_watershed_domains(cc_ctx* ctx, const float* values_dev, const uint64_t* s
                          int64_t size_filter, uint64_t* out_dev, uint64_t* max_ids_dev /* nullable, per domain */,
                          int64_t* rounds /* nullable, 2 */);
 
+/* --- Multicut: parallel greedy additive edge contraction ----------------------------------
+ * Stands where the reference's SolveGlobal calls a nifty / elf solver (multicut/solve_global.py:
+ * 148-154; neither exists here, so what follows is the definition, and parity with any of their
+ * solvers is not claimed).  uv_dev holds n_edges rows (u, v) of uint64 node ids < n_nodes,
+ * costs_dev one finite cost per row (cost_type CC_DTYPE_FLOAT32 or CC_DTYPE_FLOAT64; > 0 attractive,
+ * the reference's convention after ProbsToCosts).  All cost arithmetic is float64.
+ *   graph   a self-loop is dropped; (u, v) and (v, u) are the same edge; the costs of duplicate
+ *           rows are summed.  The contracted graph of a round has one edge per adjacent pair of
+ *           clusters, its cost the sum of all input costs between the two.  A cluster's id is the
+ *           smallest node id in it.
+ *   round r (r = 0, 1, ...) on the current contracted graph, while an edge of cost > 0 exists:
+ *           1. every cluster takes its best incident edge among those of cost > 0: the largest
+ *              cost; among equal costs the largest hash h(min, max, r) of the edge's two cluster
+ *              ids; a remaining tie would go to the smaller (min, max), but h is a bijection of
+ *              the pair for a fixed r, so none remains;
+ *           2. an edge is contracted iff it is the best edge of both its endpoints (the contracted
+ *              edges form a matching; the merged cluster takes the smaller id);
+ *           3. endpoints are relabelled, self-loops dropped, parallel edges merged by summing.
+ *           A cost of exactly 0 is never contracted.
+ *   hash    h(a, b, r) = mix((a << 32 | b) ^ ((r + 1) * 0x9E3779B97F4A7C15)) in uint64 arithmetic,
+ *           mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *           z ^= z >> 31 (the splitmix64 finalizer).
+ *   sums    the edge list is kept sorted by (min, max) with a stable sort, from the input's row
+ *           order on; a run of parallel edges is summed left to right in that order, starting from
+ *           its first entry (after a round a run holds at most 4 entries).
+ *   labels  labels_dev[i] (n_nodes uint64) = the id of node i's cluster = the smallest node id in it.
+ *   rounds  the rounds run.  n_edges = 0 or no cost > 0: the identity labelling in 0 rounds.
+ *   energy  the sum of the costs of the input rows whose endpoints got different labels, evaluated
+ *           as a balanced binary tree over the rows: x_i = (float64) cost_i for such a row, else
+ *           +0.0; x padded with +0.0 to a power of two; then pairs (x_0 + x_1), (x_2 + x_3), ...
+ *           level by level.
+ * Like sequential greedy additive contraction, a hub contracts one edge per round (a star of k
+ * attractive leaves takes k rounds).  Two calls on the same input give the same bits: the per-node
+ * maxima are 64-bit integer atomics, no sum uses a floating-point atomic.
+ * Limits, checked before the first device call: n_nodes < 2^32, n_edges < 2^31, no NULL argument.
+ * An id >= n_nodes or a non-finite cost is found by the first pass over the rows: -1 with a
+ * message, labels_dev unspecified. */
+int cc_multicut_gaec(cc_ctx* ctx, const uint64_t* uv_dev, const void* costs_dev, int cost_type, int64_t n_edges,
+                     int64_t n_nodes, uint64_t* labels_dev, int64_t* rounds, double* energy);
+/* The live edges of the contracted graph of the context's last cc_multicut_gaec: before round 0
+ * (after normalisation), before round 1, ..., after the last round.  Copies at most cap entries to
+ * out (nullable), returns their number (rounds + 1; 0 when n_edges was 0). */
+int64_t cc_multicut_live_edges(cc_ctx* ctx, int64_t* out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

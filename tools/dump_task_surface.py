@@ -40,7 +40,8 @@ def _default(param):
 
 
 # addendum name -> the modules whose tasks tests/golden/task_surface_<name>.json holds
-ADDENDA = {'watershed': ('cluster_tools_amd.watershed.watershed',)}
+ADDENDA = {'watershed': ('cluster_tools_amd.watershed.watershed',),
+           'multicut': ('cluster_tools_amd.costs.probs_to_costs', 'cluster_tools_amd.multicut.solve_global')}
 
 
 def task_surface(addendum=None):
