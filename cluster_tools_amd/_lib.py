@@ -34,6 +34,7 @@ EXPORTS = (
     'cc_region_graph', 'cc_edge_features', 'cc_label_overlaps', 'cc_max_overlaps', 'cc_affinity_features',
     'cc_distance_transform', 'cc_gaussian_smooth_domains', 'cc_local_maxima_seeds',
     'cc_watershed_height_map', 'cc_watershed_domains', 'cc_multicut_gaec', 'cc_multicut_live_edges',
+    'cc_agglomerate_mean', 'cc_agglomerate_live_edges',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -181,6 +182,8 @@ def load(host_only=False):
         'cc_watershed_domains': (I, [P, P, P, P, P, P, P, I, ctypes.c_int64, P, P, P]),
         'cc_multicut_gaec': (I, [P, P, P, I, i64, i64, P, P, P]),
         'cc_multicut_live_edges': (i64, [P, P, i64]),
+        'cc_agglomerate_mean': (I, [P, P, P, I, P, I, ctypes.c_double, i64, i64, P, P]),
+        'cc_agglomerate_live_edges': (i64, [P, P, i64]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -1180,6 +1183,40 @@ class Context:
         live = np.zeros(rounds.value + 1, dtype=np.int64)
         m = load().cc_multicut_live_edges(self._h, _ptr(live), len(live))
         return labels, {'rounds': int(rounds.value), 'energy': float(energy.value), 'live_edges': live[:max(m, 0)].tolist()}
+
+    def agglomerate(self, edges, weights, sizes, threshold, n_nodes=None, return_stats=False):
+        """Average-linkage agglomerative clustering of a weighted graph on device up to a threshold
+        (cc_agglomerate_mean; the definition is in include/cc_mi355x.h).  edges: (n, 2) CUDA tensor
+        of 8-byte node ids; weights, sizes: (n,) float32 or float64 CUDA tensors, the sizes > 0; an
+        edge between two clusters has the size-weighted mean of the weights between them, and
+        clusters merge while a mean < threshold exists (equality does not merge; +inf merges every
+        connected component); n_nodes None: edges.max() + 1.  Returns the node labels (n_nodes,) as
+        torch int64 -- a node's label is the smallest node id of its cluster -- and with
+        return_stats a dict of the rounds run and the live edges of the contracted graph before
+        each round and after the last."""
+        import torch
+        assert hasattr(edges, 'data_ptr') and edges.is_cuda and edges.element_size() == 8 and edges.is_contiguous()
+        assert edges.dim() == 2 and edges.shape[1] == 2
+        for a in (weights, sizes):
+            assert a.is_cuda and a.dtype in (torch.float32, torch.float64) and a.is_contiguous()
+            assert a.shape == (edges.shape[0],)
+        n = int(edges.shape[0])
+        if n_nodes is None:
+            n_nodes = int(edges.view(torch.int64).max()) + 1 if n else 0
+        n_nodes = int(n_nodes)
+        # the ctx runs on its own stream: the inputs may still be in flight on torch's
+        torch.cuda.current_stream(edges.device).synchronize()
+        labels = torch.empty(max(n_nodes, 0), dtype=torch.int64, device=edges.device)
+        rounds = ctypes.c_int64(0)
+        _check(load().cc_agglomerate_mean(self._h, _ptr(edges) if n else None, _ptr(weights) if n else None,
+                                          DTYPES[str(weights.dtype).split('.')[-1]], _ptr(sizes) if n else None,
+                                          DTYPES[str(sizes.dtype).split('.')[-1]], float(threshold), n, n_nodes,
+                                          _ptr(labels) if n_nodes > 0 else None, ctypes.byref(rounds)))
+        if not return_stats:
+            return labels
+        live = np.zeros(rounds.value + 1, dtype=np.int64)
+        m = load().cc_agglomerate_live_edges(self._h, _ptr(live), len(live))
+        return labels, {'rounds': int(rounds.value), 'live_edges': live[:max(m, 0)].tolist()}
 
     def evaluate(self, seg, gt, block_shape, ignore_label=0):
         """EvaluationWorkflow (evaluation/evaluation_workflow.py:46-84) on device: overlaps per

@@ -5,7 +5,8 @@
 // (cc_edge_features.hip, from affinity maps cc_affinity_features.hip), the channel / Gaussian prefilter (cc_prefilter.hip) and the seeded
 // watershed (cc_watershed.hip), the distance transform (cc_distance_transform.hip), the watershed
 // seeds (cc_seeds.hip) and the distance-transform watershed's height map, size filter and domains
-// (cc_dt_watershed.hip) and the multicut solver (cc_multicut.hip), with their C-ABI entries.
+// (cc_dt_watershed.hip), the multicut solver (cc_multicut.hip) and the agglomerative clustering
+// (cc_agglomerate.hip), with their C-ABI entries.
 //
 // A unit of its own because the HIP runtime loads a code object whole, every kernel of it, at
 // the first launch from it: kept apart, the ~60 kernels here (the prefilter's 40 template
@@ -44,3 +45,4 @@ __global__ __launch_bounds__(NTHREADS) void k_block_stats(Geom g, const float* _
 #include "cc_seeds.hip"
 #include "cc_dt_watershed.hip"
 #include "cc_multicut.hip"
+#include "cc_agglomerate.hip"

@@ -279,6 +279,7 @@ struct cc_ctx {
     int64_t nl_cap = 0;      // table slots of the last cc_label_overlaps
     int64_t nl_n = -1;       // triples the last cc_label_overlaps left in nl_sorted (-1: none)
     std::vector<int64_t> mc_live;   // live edges before round 0, 1, ... and after the last of the last cc_multicut_gaec
+    std::vector<int64_t> ag_live;   // the same of the last cc_agglomerate_mean
     // last run
     int64_t n_blocks = 0;
     uint64_t n_labels = 0;

@@ -13,15 +13,21 @@ reference.  What is not built raises NotImplementedError:
   * agglomerate_ws, two_pass_ws (options of that workflow) and sanity_checks
     (CheckSubGraphsWorkflow: there are no per-block sub-graphs to check) must be False;
   * n_scales must be 0 (multicut/multicut_workflow.py), rf_path '' (costs/costs_workflow.py).
-target must be 'local'."""
+target must be 'local'.
+
+AgglomerativeClusteringWorkflow (reference: workflows.py:326-357) is the second entry point on the
+same problem file: ProblemWorkflow without the costs, then the AgglomerativeClustering task on the
+edge features (problem_path:features) up to `threshold`, then Write (identifier
+'agglomerative_clustering').  The same settings are not built."""
 import os
 
-from cluster_tools_amd.luigi_compat import Parameter, IntParameter, BoolParameter, DictParameter
+from cluster_tools_amd.luigi_compat import Parameter, IntParameter, FloatParameter, BoolParameter, DictParameter
 from cluster_tools_amd.cluster_tasks import WorkflowBase
 from cluster_tools_amd.graph import GraphWorkflow
 from cluster_tools_amd.features import EdgeFeaturesWorkflow
 from cluster_tools_amd.costs import EdgeCostsWorkflow
 from cluster_tools_amd.multicut import MulticutWorkflow
+from cluster_tools_amd.agglomerative_clustering import agglomerative_clustering as agglomerate_tasks
 from cluster_tools_amd.write import write as write_tasks
 
 
@@ -141,4 +147,27 @@ class MulticutSegmentationWorkflow(SegmentationWorkflowBase):
         config = SegmentationWorkflowBase.get_config()
         config.update(MulticutWorkflow.get_config())
         config.update({'write': write_tasks.WriteLocal.default_task_config()})
+        return config
+
+
+class AgglomerativeClusteringWorkflow(SegmentationWorkflowBase):
+    threshold = FloatParameter()
+
+    def _agglomerate_task(self, dep):
+        agglomerate_task = getattr(agglomerate_tasks, self._get_task_name('AgglomerativeClustering'))
+        return agglomerate_task(tmp_folder=self.tmp_folder, max_jobs=self.max_jobs, config_dir=self.config_dir,
+                                problem_path=self.problem_path, assignment_path=self.output_path,
+                                assignment_key=self.node_labels_key, features_path=self.problem_path,
+                                features_key=self.features_key, threshold=self.threshold, dependency=dep)
+
+    def requires(self):
+        dep = self._watershed_tasks()
+        dep = self._problem_tasks(dep, compute_costs=False)
+        dep = self._agglomerate_task(dep)
+        return self._write_tasks(dep, 'agglomerative_clustering')
+
+    @staticmethod
+    def get_config():
+        config = SegmentationWorkflowBase.get_config()
+        config.update({'agglomerative_clustering': agglomerate_tasks.AgglomerativeClusteringLocal.default_task_config()})
         return config

@@ -741,6 +741,55 @@ int cc_multicut_gaec(cc_ctx* ctx, const uint64_t* uv_dev, const void* costs_dev,
  * out (nullable), returns their number (rounds + 1; 0 when n_edges was 0). */
 int64_t cc_multicut_live_edges(cc_ctx* ctx, int64_t* out, int64_t cap);
 
+/* --- Agglomerative clustering: parallel average linkage up to a threshold -------------------
+ * Stands where the reference's AgglomerativeClustering job calls elf's mala_clustering
+ * (agglomerative_clustering/agglomerative_clustering.py:138; neither elf nor nifty exists here, so
+ * what follows is the definition: the size-weighted MEAN of the edge weights, not MALA's histogram
+ * median, and parity with it is not claimed).  uv_dev holds n_edges rows (u, v) of uint64 node ids
+ * < n_nodes, weights_dev one finite weight per row and sizes_dev one finite size > 0 per row (each
+ * CC_DTYPE_FLOAT32 or CC_DTYPE_FLOAT64).  All arithmetic is float64.
+ *   graph    a self-loop is dropped; (u, v) and (v, u) are the same edge.  The contracted graph of
+ *            a round has one edge per adjacent pair of clusters, which carries S = sum w_i * s_i
+ *            and Z = sum s_i over all input rows i between the two.  Each w_i * s_i is one float64
+ *            product, rounded and stored before any addition (never fused into a sum).  A
+ *            cluster's id is the smallest node id in it.
+ *   priority p = S / Z, one IEEE float64 division; a quotient that compares equal to 0 is replaced
+ *            by +0.0 (p == 0 ? +0.0 : p), so -0.0 and +0.0 are one priority.  An edge is eligible
+ *            iff p < threshold: equality does not merge.
+ *   round r  (r = 0, 1, ...) on the current contracted graph, while an eligible edge exists:
+ *            1. every cluster takes its best incident eligible edge: the smallest p; among equal p
+ *               the largest hash h(min, max, r) of the edge's two cluster ids, the multicut's h
+ *               above (a bijection of the pair for a fixed r, so no tie remains);
+ *            2. an edge is contracted iff it is the best edge of both its endpoints (the contracted
+ *               edges form a matching; the merged cluster takes the smaller id);
+ *            3. endpoints are relabelled, self-loops dropped, parallel edges merged by summing S
+ *               and summing Z.
+ *   sums     the edge list is kept sorted by (min, max) with a stable sort, from the input's row
+ *            order on; a run of parallel edges is summed left to right in that order, starting from
+ *            its first entry, S and Z each on its own.
+ *   labels   labels_dev[i] (n_nodes uint64) = the id of node i's cluster = the smallest node id in it.
+ *   rounds   the rounds run.  threshold = +inf: every connected component becomes one cluster (an
+ *            edge whose p is +inf or a NaN after an overflow of S stays uncontracted);
+ *            threshold = -inf: nothing merges.
+ * The mean is reducible -- the p between i + j and k is a weighted average of p(i, k) and p(j, k),
+ * or the one of them that exists, so never below the smaller --, hence contracting all mutually best
+ * edges per round yields the partition of sequential smallest-first agglomeration stopped at the
+ * threshold, provided no two compared priorities are equal.  A hub contracts one edge per round (a
+ * star of k eligible leaves takes k rounds).  Two calls on the same input give the same bits: the
+ * per-node minima are 64-bit integer atomics on an order-reversing key of p, no sum uses a
+ * floating-point atomic.
+ * Limits, checked before the first device call: n_nodes < 2^32, n_edges < 2^31, no NULL argument,
+ * pointers aligned to their element, the threshold not a NaN.  An id >= n_nodes, a non-finite
+ * weight or a size that is not finite and > 0 is found by the first pass over the rows: -1 with a
+ * message, labels_dev unspecified. */
+int cc_agglomerate_mean(cc_ctx* ctx, const uint64_t* uv_dev, const void* weights_dev, int weight_type,
+                        const void* sizes_dev, int size_type, double threshold, int64_t n_edges, int64_t n_nodes,
+                        uint64_t* labels_dev, int64_t* rounds);
+/* The live edges of the contracted graph of the context's last cc_agglomerate_mean: before round 0
+ * (after normalisation), before round 1, ..., after the last round.  Copies at most cap entries to
+ * out (nullable), returns their number (rounds + 1; the one entry is 0 when n_edges was 0). */
+int64_t cc_agglomerate_live_edges(cc_ctx* ctx, int64_t* out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif
