@@ -34,7 +34,7 @@ EXPORTS = (
     'cc_region_graph', 'cc_edge_features', 'cc_label_overlaps', 'cc_max_overlaps', 'cc_affinity_features',
     'cc_distance_transform', 'cc_gaussian_smooth_domains', 'cc_local_maxima_seeds',
     'cc_watershed_height_map', 'cc_watershed_domains', 'cc_multicut_gaec', 'cc_multicut_live_edges',
-    'cc_agglomerate_mean', 'cc_agglomerate_live_edges',
+    'cc_agglomerate_mean', 'cc_agglomerate_live_edges', 'cc_graph_watershed', 'cc_graph_components',
 )
 # redo flags of the one-read-back schedule (RF_* in csrc/cc_kernels.hip)
 RF_BIG, RF_ROOTS, RF_CUBES, RF_PAIRS, RF_IOVF = 1, 2, 4, 8, 16
@@ -184,6 +184,8 @@ def load(host_only=False):
         'cc_multicut_live_edges': (i64, [P, P, i64]),
         'cc_agglomerate_mean': (I, [P, P, P, I, P, I, ctypes.c_double, i64, i64, P, P]),
         'cc_agglomerate_live_edges': (i64, [P, P, i64]),
+        'cc_graph_watershed': (I, [P, P, P, I, P, i64, i64, P, P]),
+        'cc_graph_components': (I, [P, P, P, i64, i64, I, P, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -1217,6 +1219,54 @@ class Context:
         live = np.zeros(rounds.value + 1, dtype=np.int64)
         m = load().cc_agglomerate_live_edges(self._h, _ptr(live), len(live))
         return labels, {'rounds': int(rounds.value), 'live_edges': live[:max(m, 0)].tolist()}
+
+    def graph_watershed(self, edges, weights, seeds, n_nodes=None, return_stats=False):
+        """Seeded edge-weighted watershed on a graph on device (cc_graph_watershed; the definition
+        is in include/cc_mi355x.h).  edges: (n, 2) CUDA tensor of 8-byte node ids; weights: (n,)
+        float32 or float64 CUDA tensor, the smaller the earlier, ties by the row index; seeds:
+        (n_nodes,) CUDA tensor of 8-byte labels, 0 = unlabelled; n_nodes None: len(seeds).  Returns
+        the node labels (n_nodes,) as torch int64 -- the seeds grown along the smallest edges, 0
+        where no seed reaches -- and with return_stats a dict of the rounds run."""
+        import torch
+        assert hasattr(edges, 'data_ptr') and edges.is_cuda and edges.element_size() == 8 and edges.is_contiguous()
+        assert edges.dim() == 2 and edges.shape[1] == 2
+        assert weights.is_cuda and weights.dtype in (torch.float32, torch.float64) and weights.is_contiguous()
+        assert weights.shape == (edges.shape[0],)
+        assert seeds.is_cuda and seeds.element_size() == 8 and seeds.is_contiguous() and seeds.dim() == 1
+        n = int(edges.shape[0])
+        n_nodes = int(seeds.shape[0]) if n_nodes is None else int(n_nodes)
+        assert seeds.shape[0] == n_nodes, '%i, %i' % (seeds.shape[0], n_nodes)
+        # the ctx runs on its own stream: the inputs may still be in flight on torch's
+        torch.cuda.current_stream(edges.device).synchronize()
+        labels = torch.empty(max(n_nodes, 0), dtype=torch.int64, device=edges.device)
+        rounds = ctypes.c_int64(0)
+        _check(load().cc_graph_watershed(self._h, _ptr(edges) if n else None, _ptr(weights) if n else None,
+                                         DTYPES[str(weights.dtype).split('.')[-1]], _ptr(seeds) if n_nodes > 0 else None,
+                                         n, n_nodes, _ptr(labels) if n_nodes > 0 else None, ctypes.byref(rounds)))
+        return (labels, {'rounds': int(rounds.value)}) if return_stats else labels
+
+    def graph_components(self, edges, node_labels, n_nodes=None, ignore_background=True):
+        """Connected components of a node labelling on a graph on device (cc_graph_components; the
+        definition is in include/cc_mi355x.h).  edges: (n, 2) CUDA tensor of 8-byte node ids;
+        node_labels: (n_nodes,) CUDA tensor of 8-byte labels; n_nodes None: len(node_labels).  Two
+        nodes share a component iff a path of edges joins them inside one label; with
+        ignore_background the nodes of label 0 get 0.  Returns (components, n_components): the
+        (n_nodes,) torch int64 numbers 1, 2, ... in the order of each component's smallest node id."""
+        import torch
+        assert hasattr(edges, 'data_ptr') and edges.is_cuda and edges.element_size() == 8 and edges.is_contiguous()
+        assert edges.dim() == 2 and edges.shape[1] == 2
+        assert node_labels.is_cuda and node_labels.element_size() == 8 and node_labels.is_contiguous()
+        assert node_labels.dim() == 1
+        n = int(edges.shape[0])
+        n_nodes = int(node_labels.shape[0]) if n_nodes is None else int(n_nodes)
+        assert node_labels.shape[0] == n_nodes, '%i, %i' % (node_labels.shape[0], n_nodes)
+        torch.cuda.current_stream(edges.device).synchronize()
+        out = torch.empty(max(n_nodes, 0), dtype=torch.int64, device=edges.device)
+        n_comp = ctypes.c_uint64(0)
+        _check(load().cc_graph_components(self._h, _ptr(edges) if n else None, _ptr(node_labels) if n_nodes > 0 else None,
+                                          n, n_nodes, 1 if ignore_background else 0,
+                                          _ptr(out) if n_nodes > 0 else None, ctypes.byref(n_comp)))
+        return out, int(n_comp.value)
 
     def evaluate(self, seg, gt, block_shape, ignore_label=0):
         """EvaluationWorkflow (evaluation/evaluation_workflow.py:46-84) on device: overlaps per

@@ -6,10 +6,11 @@
 // watershed (cc_watershed.hip), the distance transform (cc_distance_transform.hip), the watershed
 // seeds (cc_seeds.hip) and the distance-transform watershed's height map, size filter and domains
 // (cc_dt_watershed.hip), the multicut solver (cc_multicut.hip) and the agglomerative clustering
-// (cc_agglomerate.hip), with their C-ABI entries.
+// (cc_agglomerate.hip), the graph watershed and the graph components of a node labelling
+// (cc_graph_postprocess.hip), with their C-ABI entries.
 //
 // A unit of its own because the HIP runtime loads a code object whole, every kernel of it, at
-// the first launch from it: kept apart, the ~60 kernels here (the prefilter's 40 template
+// the first launch from it: kept apart, the ~75 kernels here (the prefilter's 40 template
 // instances alone) are loaded only by the jobs that use them, and a one-shot labelling job's
 // first call loads the labelling path's code object only (profiles/r04_cold_split.jsonl: the
 // first cc_label_volume of a fresh process 5.3 -> 3.9-4.1 ms, dlopen 0.87 -> 0.5 ms).
@@ -46,3 +47,4 @@ __global__ __launch_bounds__(NTHREADS) void k_block_stats(Geom g, const float* _
 #include "cc_dt_watershed.hip"
 #include "cc_multicut.hip"
 #include "cc_agglomerate.hip"
+#include "cc_graph_postprocess.hip"

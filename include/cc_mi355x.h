@@ -790,6 +790,70 @@ int cc_agglomerate_mean(cc_ctx* ctx, const uint64_t* uv_dev, const void* weights
  * out (nullable), returns their number (rounds + 1; the one entry is 0 when n_edges was 0). */
 int64_t cc_agglomerate_live_edges(cc_ctx* ctx, int64_t* out, int64_t cap);
 
+/* --- Graph watershed: seeded edge-weighted watershed on a graph -----------------------------
+ * Stands where the reference's GraphWatershedAssignments job calls nifty's
+ * edgeWeightedWatershedsSegmentation (postprocess/graph_watershed_assignments.py:171; nifty does
+ * not exist here, so what follows is the definition, and parity with nifty's function is not
+ * claimed beyond it).  uv_dev holds n_edges rows (u, v) of uint64 node ids < n_nodes, weights_dev
+ * one finite weight per row (weight_type CC_DTYPE_FLOAT32 or CC_DTYPE_FLOAT64, compared as
+ * float64), seeds_dev n_nodes uint64 values, 0 = unlabelled.
+ *   order    a row is ordered by (weight, row index), ascending: a strict total order.  -0.0 and
+ *            +0.0 are one weight.  A self-loop is dropped; (u, v) and (v, u) are the same edge;
+ *            duplicate rows are separate edges.
+ *   flood    the definition.  A queue holds every edge between a labelled and an unlabelled node.
+ *            Pop the smallest edge; if its far end is still unlabelled, that end takes the near
+ *            end's label and its own edges to unlabelled nodes enter the queue.  Continue until the
+ *            queue is empty.  A node that no seed reaches keeps 0; seeds never change.
+ *   rounds   what runs, and gives the flood's labels: with a strict order the flood is the minimum
+ *            spanning forest rooted at the seeds.  A cluster is a set of contracted nodes, at first
+ *            every node its own; it is labelled iff it holds a seed.  Per round every UNLABELLED
+ *            cluster that has an edge to another cluster takes its smallest such edge and is
+ *            contracted along it; two unlabelled clusters that pick each other form one cluster, a
+ *            cluster contracted into a labelled one takes that label.  Labelled clusters pick
+ *            nothing; an edge between two labelled clusters is dead.  The contraction of a round is
+ *            a forest, not a matching.  The rounds end when no unlabelled cluster has an outgoing
+ *            edge; at most floor(log2(unlabelled nodes)) + 1 are run.  Without any seed every
+ *            label is 0 whatever is contracted: no round is run.
+ *   labels   labels_dev[i] (n_nodes uint64) = the label of node i's cluster, 0 if it has none.
+ *            labels_dev may be seeds_dev.
+ *   rounds   the rounds run.  n_edges = 0, no seed, or no unlabelled node next to an edge:
+ *            labels = seeds in 0 rounds.
+ * Two seeds of one label stay two clusters (the edge between them is dead); the result is as if
+ * they were one.  Two calls on the same input give the same bits: a cluster's smallest edge is
+ * found by integer atomic minima only, first of the order-preserving 64-bit key of the weight,
+ * then of the row index among the edges that hold it.
+ * Limits, checked before the first device call: n_nodes < 2^32, n_edges < 2^31, no NULL argument,
+ * pointers aligned to their element.  An id >= n_nodes or a non-finite weight is found by the
+ * first pass over the rows: -1 with a message, labels_dev unspecified (untouched so far). */
+int cc_graph_watershed(cc_ctx* ctx, const uint64_t* uv_dev, const void* weights_dev, int weight_type,
+                       const uint64_t* seeds_dev, int64_t n_edges, int64_t n_nodes, uint64_t* labels_dev,
+                       int64_t* rounds);
+
+/* --- Graph components: connected components of a node labelling on a graph ------------------
+ * Stands where the reference's GraphConnectedComponents job calls nifty's
+ * connectedComponentsFromNodeLabels and then relabelConsecutive(start_label=1, keep_zeros=True)
+ * (postprocess/graph_connected_components.py:110-114).  nifty's numbering of the components is not
+ * known here: equality with the reference holds as a partition, not id for id.
+ *   components  two nodes are in one component iff a path of edges joins them whose nodes all
+ *            carry the same value in node_labels_dev (n_nodes uint64).  uv_dev as above; self-loops
+ *            and duplicate rows change nothing.
+ *   background  with ignore_background != 0 a node of input label 0 gets 0 and takes no part;
+ *            with 0, label-0 nodes form components like any others.
+ *   out      out_dev[i] (n_nodes uint64; not node_labels_dev) = the number of node i's component:
+ *            the components are numbered 1, 2, ... in the order of their smallest node id.
+ *            *n_components = their number.
+ * Hooking by integer atomic minima on a parent array that only points to smaller node ids, and
+ * pointer jumping, until a round hooks nothing: the final roots are the components' smallest
+ * nodes whatever the order of the atomics, so two calls give the same bits.  A round that hooks
+ * takes at least one root away, so the rounds end; no bound on their number below that is claimed
+ * (an unlucky order of the node ids can need many), and every round and every pointer-jumping
+ * launch costs one host read-back.
+ * Limits, checked before the first device call: n_nodes < 2^32, n_edges < 2^31, no NULL argument,
+ * aligned pointers, out_dev != node_labels_dev.  An id >= n_nodes is found by the first pass over the rows: -1 with a
+ * message, out_dev unspecified. */
+int cc_graph_components(cc_ctx* ctx, const uint64_t* uv_dev, const uint64_t* node_labels_dev, int64_t n_edges,
+                        int64_t n_nodes, int ignore_background, uint64_t* out_dev, uint64_t* n_components);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,9 @@ def _default(param):
 # addendum name -> the modules whose tasks tests/golden/task_surface_<name>.json holds
 ADDENDA = {'watershed': ('cluster_tools_amd.watershed.watershed',),
            'multicut': ('cluster_tools_amd.costs.probs_to_costs', 'cluster_tools_amd.multicut.solve_global'),
-           'agglomerative_clustering': ('cluster_tools_amd.agglomerative_clustering.agglomerative_clustering',)}
+           'agglomerative_clustering': ('cluster_tools_amd.agglomerative_clustering.agglomerative_clustering',),
+           'graph_postprocess': ('cluster_tools_amd.postprocess.graph_connected_components',
+                                 'cluster_tools_amd.postprocess.graph_watershed_assignments')}
 
 
 def task_surface(addendum=None):
